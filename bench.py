@@ -13,11 +13,16 @@ Metric: frame-pairs/s over the whole job (all ranks).  One process per GPU (torc
 pairs are independent, so each rank runs its own batch of 8 ("weak" scaling, no data-path
 collective; timing is max over ranks via one all_reduce after the timed region).
 
-Also reported: roofline of the dominant kernel per step (GEMM: one launch; lookup: 12 launches),
-measured live with HIP events on the launch stream (the GEMM launch alone, the 12 lookups as one
-bracket), both kernels' rooflines and the GEMM's MFMA fraction, and the CPU oracle
-(test infrastructure, numpy/BLAS float32 restatement of the reference path) timed on a bounded
-sample on this host, rank 0 only.
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: set up, warm up, time the K
+steps, print the result line.  `--dump-outputs DIR` also writes what the last timed step returned
+(DIR/<name>.npy, float32; the inputs are seeded, so two builds can be compared output for output).
+
+`--full` adds everything else to the line: roofline of the dominant kernel per step (GEMM: one launch;
+lookup: 12 launches), measured live with HIP events on the launch stream (the GEMM launch alone, the
+12 lookups as one bracket), both kernels' rooflines and the GEMM's MFMA fraction, live counter passes,
+the fp32-mode leg, the model-level / DICL / hybrid / training / high-resolution legs (each with its
+own on/off switch) and the CPU baseline (test infrastructure: the reference's eager path on torch-CPU)
+timed on a bounded sample on this host, rank 0 only.
 """
 
 import argparse
@@ -53,6 +58,13 @@ def parse():
     ap.add_argument("--radius", type=int, default=4)
     ap.add_argument("--levels", type=int, default=4)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp32-f32", "fp32-s24", "fp32-exact", "bf16-f32", "fp32-f16"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-kernel HIP events and rooflines, "
+                         "live counter passes, the fp32-mode leg, the model-level / DICL / hybrid / training / "
+                         "high-resolution legs and the CPU baseline (each leg's own switch below still applies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32, at most 60 MB in all: a fixed seeded sample of a larger array)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=10.0)
     ap.add_argument("--event-every", type=int, default=5,
@@ -89,7 +101,10 @@ def parse():
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0 (pair with --backend gloo)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/collective plumbing only (no GPU work): for the CPU gloo tests")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def maybe_launch(args):
@@ -605,10 +620,11 @@ def host_barrier():
 HBM_COPY_GBS = 6290.0          # measured float4 copy rate (MI355X_MICROARCH.md chip table)
 
 
-def corr_leg(args, precision, inputs, world, device, steps, warmup):
+def corr_leg(args, precision, inputs, world, device, steps, warmup, events=True):
     """Time `steps` hot-path steps (operand prep + correlation GEMM + `iters` lookups) after `warmup`
-    untimed ones, bracketed by barrier + synchronize, job time = MAX over ranks; HIP events on the launch
-    stream around the GEMM launch alone and around the lookups of every E-th timed step (never the first)."""
+    untimed ones, bracketed by barrier + synchronize, job time = MAX over ranks; with `events`, HIP events
+    on the launch stream around the GEMM launch alone and around the lookups of every E-th timed step
+    (never the first).  Also returns what the last timed step returned (its last lookup's output)."""
     ev_gemm, ev_look = [], []
     if args.dry_run:
         def step(record):
@@ -643,14 +659,36 @@ def corr_leg(args, precision, inputs, world, device, steps, warmup):
         torch.distributed.barrier()
     sync()
     E = max(1, args.event_every)
+    last = steps - 1
     t0 = time.perf_counter()
-    for i in range(steps):
-        step(i % E == E - 1)
+    for i in range(last):
+        step(events and i % E == E - 1)
+    out = step(events and last % E == E - 1)     # only the last step's result is kept (none alive before)
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
         torch.distributed.barrier()
-    return job_time(elapsed, world, device), ev_gemm, ev_look
+    return job_time(elapsed, world, device), ev_gemm, ev_look, out
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6
+
+
+def dump_outputs(directory, arrays, rank, world):
+    """--dump-outputs: each tensor of `arrays` as DIR/<name>.npy in float32 (ranks > 0: <name>.rank<r>.npy),
+    the job's files within DUMP_LIMIT_BYTES in all.  A tensor over its share is written as a 1-D sample of
+    its flattened elements at fixed positions (seed 0, ascending), the same in every run and build."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (4 * max(1, world) * max(1, len(arrays)))
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), share, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(directory, name + (f".rank{rank}" if rank else "") + ".npy"), a)
 
 
 def child_env(device):
@@ -874,7 +912,11 @@ def main():
     B = args.batch
 
     inputs = None if args.dry_run else rank_inputs(args, rank, world, h8, w8, device)
-    elapsed, ev_gemm, ev_look = corr_leg(args, args.precision, inputs, world, device, args.steps, args.warmup)
+    elapsed, ev_gemm, ev_look, last_out = corr_leg(args, args.precision, inputs, world, device, args.steps,
+                                                   args.warmup, events=args.full)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {} if last_out is None else {"corr_lookup_last": last_out}, rank, world)
+    del last_out
 
     s = storage_bytes(args.precision)
     compute_dt = "fp32" if args.precision.startswith("fp32") else "bf16"
@@ -904,9 +946,9 @@ def main():
     }
     if args.dry_run:
         res["dry_run"] = "launcher / collective plumbing only: no GPU work, value meaningless"
-        if args.model_level == "on":
+        if args.full and args.model_level == "on":
             res["model_level"] = model_leg(args, world, rank, device)
-    else:
+    elif args.full:
         # rank 0 profiles its own GPU in child processes after the timed region (the other ranks go on
         # to the next leg and wait for rank 0 at its first barrier)
         live = rank == 0 and args.live_pmc == "on"
@@ -917,7 +959,7 @@ def main():
         if fp32_leg:
             progress(rank, "fp32_mode leg")
             w32 = max(3, args.warmup)
-            el32, eg32, el32l = corr_leg(args, "fp32", inputs, world, device, args.fp32_steps, w32)
+            el32, eg32, el32l = corr_leg(args, "fp32", inputs, world, device, args.fp32_steps, w32)[:3]
         traffic, note = live_traffic(args, args.precision, B, rank, device) if live else (None, "")
         if traffic is None:
             fallback, fnote = stored_traffic(args.precision)
@@ -964,7 +1006,7 @@ def main():
                 torch.cuda.empty_cache()
             if rank == 0:
                 res[key] = out
-    if rank == 0 and world == 1 and not args.dry_run and args.highres == "on":
+    if args.full and rank == 0 and world == 1 and not args.dry_run and args.highres == "on":
         progress(rank, "highres_fs leg")
         try:
             res["highres_fs"] = highres_leg(args, args.precision)
@@ -972,7 +1014,7 @@ def main():
             res["highres_fs"] = {"error": f"{type(e).__name__}: {e}"[:500]}
         torch.cuda.empty_cache()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after every GPU leg: the other ranks wait at the barrier below
             progress(rank, "cpu_baseline leg")
             res["cpu_baseline"] = cpu_baseline(args)

@@ -201,7 +201,7 @@ def test_bench_model_level_leg_is_batch_sharded(gb):
     import subprocess
     env = dict(os.environ, OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--backend", "gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--backend", "gloo", "--full",
            "--no-cpu-baseline", "--steps", "1", "--warmup", "0"] + (["--global-batch", str(gb)] if gb else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -223,8 +223,8 @@ def test_bench_rank0_cpu_baseline_at_two_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--backend",
-                          "gloo", "--steps", "1", "--warmup", "0", "--model-level", "off", "--cpu-budget-s", "0.5"],
-                         capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                          "gloo", "--full", "--steps", "1", "--warmup", "0", "--model-level", "off",
+                          "--cpu-budget-s", "0.5"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

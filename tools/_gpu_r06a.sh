@@ -27,7 +27,7 @@ done
 HL="--no-cpu-baseline --model-level off --fp32-mode off --live-pmc off --train off --hybrid off --dicl off --highres off"
 for round in 1 2; do
   for v in product w8auxh0; do
-    RMD_LIBRARY=$(lib $v) timeout -k 10 200 python3 -u bench.py $HL > $R/b_${v}_$round.json 2> $R/b.err || { tail $R/b.err; exit 5; }
+    RMD_LIBRARY=$(lib $v) timeout -k 10 200 python3 -u bench.py --full $HL > $R/b_${v}_$round.json 2> $R/b.err || { tail $R/b.err; exit 5; }
     python3 -c "
 import json;d=json.loads(open('$R/b_${v}_$round.json').read().splitlines()[-1])
 print('$v', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['avg_launch_ms'], d['roofline_gemm']['avg_launch_ms'])"

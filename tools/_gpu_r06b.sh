@@ -29,7 +29,7 @@ for v in product; do
   done
 done
 HL="--no-cpu-baseline --model-level off --live-pmc off --train off --hybrid off --dicl off --highres off"
-timeout -k 10 300 python3 -u bench.py $HL > $R/b.json 2> $R/b.err || { tail $R/b.err; exit 5; }
+timeout -k 10 300 python3 -u bench.py --full $HL > $R/b.json 2> $R/b.err || { tail $R/b.err; exit 5; }
 python3 -c "
 import json;d=json.loads(open('$R/b.json').read().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline_gemm']['avg_launch_ms'])

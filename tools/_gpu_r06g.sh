@@ -16,7 +16,7 @@ done
 HL="--no-cpu-baseline --model-level off --live-pmc off --train off --hybrid off --dicl off --highres off"
 for round in 1 2; do
   for v in product free; do
-    RMD_LIBRARY=$(lib $v) timeout -k 10 300 python3 -u bench.py $HL > $R/b_${v}_$round.json 2> $R/b.err || { tail $R/b.err; exit 5; }
+    RMD_LIBRARY=$(lib $v) timeout -k 10 300 python3 -u bench.py --full $HL > $R/b_${v}_$round.json 2> $R/b.err || { tail $R/b.err; exit 5; }
     python3 -c "
 import json;d=json.loads(open('$R/b_${v}_$round.json').read().splitlines()[-1])
 f=d['fp32_mode']; print('$v', d['value'], 'fp32', f['value'], f['roofline_gemm']['avg_launch_ms'])"

@@ -4,7 +4,7 @@ set -o pipefail
 export TMPDIR=/tmp
 R=gpurun_out/r06l
 mkdir -p $R
-timeout -k 10 900 python3 -u bench.py --gpus 8 --backend gloo --one-device --steps 5 --warmup 2 --fp32-steps 3 \
+timeout -k 10 900 python3 -u bench.py --full --gpus 8 --backend gloo --one-device --steps 5 --warmup 2 --fp32-steps 3 \
   --model-level off --train off --hybrid off --dicl off --highres off --no-cpu-baseline > $R/bench8.json 2> $R/bench8.err || { tail -30 $R/bench8.err; exit 2; }
 python3 -c "
 import json;d=json.loads([l for l in open('$R/bench8.json').read().splitlines() if l.startswith('{')][-1])

@@ -17,7 +17,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $R/tests.log
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $R/smoke.log 2>&1 || { tail $R/smoke.log; exit 5; }
 tail -4 $R/smoke.log
-timeout -k 10 600 python3 -u bench.py --steps 20 --warmup 5 > $R/bench.json 2> $R/bench.err || { tail -20 $R/bench.err; exit 6; }
+timeout -k 10 600 python3 -u bench.py --full --steps 20 --warmup 5 > $R/bench.json 2> $R/bench.err || { tail -20 $R/bench.err; exit 6; }
 python3 -c "
 import json;d=json.loads(open('$R/bench.json').read().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['avg_launch_ms'], d['roofline_gemm']['avg_launch_ms'])
