@@ -436,6 +436,63 @@ int rmd_input_flow(const float* flow, const unsigned char* valid, int batch, int
                    int padded_height, int padded_width, int pad_top, int pad_left, float flow_inf, float* flow_out,
                    unsigned char* valid_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sequence losses (the part of a training step the reference keeps in its model package).  One
+ * operation covers the four loss types:
+ *   raft/sequence               SequenceLoss.compute, src/models/impls/raft.py:616-644
+ *   raft+dicl/mlseq             MultiLevelSequenceLoss.compute + upsample, src/models/common/loss/mlseq.py:34-67
+ *   raft+dicl/mlseq-restricted  RestrictedMultiLevelSequenceLoss.compute, src/models/impls/raft_dicl_ctf_l3.py:430-473
+ *   dicl/multiscale             MultiscaleLoss.compute + upsample, src/models/impls/dicl.py:436-472
+ * For npred predictions flow_k (B, 2, h_k, w_k) float32 against target (B, 2, H, W) and a validity
+ * mask (B, H, W) of bytes (non-zero = set; a prediction's own `mask` replaces the shared `valid`):
+ *   f    = flow_k where (h_k, w_k) == (H, W), else its bilinear align_corners=True upsample with
+ *          component 0 times W/w_k and component 1 times H/h_k (mlseq.py:59-67; ATen's index rule:
+ *          source = dst * ((in-1)/(out-1)) in fp32, 0 for out == 1, i0 = floor, i1 = i0 + (i0 < in-1))
+ *   dist = |d0|+|d1| (RMD_LOSS_L1), sqrt(d0^2+d1^2) (RMD_LOSS_L2), (|d0|+|d1|)/2 (RMD_LOSS_ABSMEAN,
+ *          raft.py:627-628), (|d0|+|d1|+1e-8)^0.4 (RMD_LOSS_ROBUST, dicl.py:450-451), d = f - target
+ *   S_k  = sum of dist over set pixels (a selection: raft.py:639), N_k = their number; with
+ *          include_invalid S_k = sum of dist * mask (a product: raft.py:633) and N_k = B*H*W
+ *   loss = scale * sum_k weight_k * S_k / N_k
+ * N_k == 0 gives NaN as mean() of an empty tensor does; with skip_empty such a prediction adds exactly
+ * 0 (`if torch.any(valid_lvl)`, raft_dicl_ctf_l3.py:453, decided on the device).  `loss` is 1 float,
+ * `counts` npred 64-bit integers (N_k, read again by the backward), `workspace`
+ * rmd_sequence_loss_workspace_bytes() bytes.  Per-block partial sums are added in a fixed order in
+ * double: no atomics, bitwise reproducible.  At most RMD_LOSS_MAX_PREDICTIONS per call (the table is a
+ * kernel argument); a caller chunks longer lists and adds the chunk losses.
+ */
+#define RMD_LOSS_MAX_PREDICTIONS 32
+#define RMD_LOSS_L1 1
+#define RMD_LOSS_L2 2
+#define RMD_LOSS_ABSMEAN 3
+#define RMD_LOSS_ROBUST 4
+
+typedef struct rmd_loss_prediction {
+    const float* flow;             /* (B, 2, height, width)                                           */
+    const unsigned char* mask;     /* own (B, H, W) mask, or NULL: the call's shared `valid`           */
+    float* grad;                   /* backward: (B, 2, height, width) output, NULL = none required     */
+    int height, width;
+    float weight;
+} rmd_loss_prediction;
+
+size_t rmd_sequence_loss_workspace_bytes(int batch, int height, int width, int npred);
+int rmd_sequence_loss(const rmd_loss_prediction* preds, int npred, const float* target, const unsigned char* valid,
+                      int batch, int height, int width, int norm, int include_invalid, int skip_empty, float scale,
+                      float* loss, long long* counts, void* workspace, void* stream);
+
+/* Gradients of rmd_sequence_loss (autograd of the lines above), recomputed from the inputs: nothing
+ * is saved by the forward but `counts`.  grad_loss (1 float, the upstream gradient) and counts are
+ * read from DEVICE memory.  Every preds[k].grad that is not NULL is overwritten:
+ *   full resolution: grad = grad_loss * scale * weight_k / N_k * m(p) * d dist / d d_c, with
+ *     sign(d_c) (sign(0) = 0) for L1, half that for ABSMEAN, d_c/|d| (0 where |d| = 0, as torch's norm
+ *     backward) for L2, 0.4 (|d0|+|d1|+1e-8)^-0.6 sign(d_c) for ROBUST;
+ *   upsampled: the transpose of the bilinear map in gather form (each coarse pixel sums the fine
+ *     pixels whose i0 / i1 select it, in a fixed order) — no atomics, bitwise reproducible.
+ * N_k == 0 gives an all-zero gradient. */
+int rmd_sequence_loss_backward(const rmd_loss_prediction* preds, int npred, const float* target,
+                               const unsigned char* valid, int batch, int height, int width, int norm,
+                               int include_invalid, float scale, const float* grad_loss, const long long* counts,
+                               void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

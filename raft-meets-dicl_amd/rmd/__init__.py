@@ -14,9 +14,13 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
   rmd.warp.warp_backwards               <- src/models/common/warp.py:5-33
   rmd.raft.Up8Network / SoftArgMax*     <- src/models/impls/raft.py:98-190,299-331 (rmd.heads)
   rmd.input.InputSpec / ModuloPadding   <- src/models/input.py:32-313 (frame pair + flow target format)
+  rmd.loss.SequenceLoss / MultiLevelSequenceLoss / RestrictedMultiLevelSequenceLoss / MultiscaleLoss
+                                        <- raft.py:596-644, common/loss/mlseq.py, raft_dicl_ctf_l3.py:401-473,
+                                           dicl.py:416-472 (one fused forward + backward, rmd.ops.sequence_loss)
 """
 
-from . import blocks, config, corr, cpu, dicl, heads, input, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
+from . import blocks, config, corr, cpu, dicl, heads, input, loss, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
+from .loss import MultiLevelSequenceLoss, MultiscaleLoss, RestrictedMultiLevelSequenceLoss, SequenceLoss  # noqa: F401
 from .ops import set_default_precision, get_default_precision  # noqa: F401
 
 __version__ = "0.1"

@@ -35,6 +35,19 @@ class PyramidDesc(ctypes.Structure):
     ]
 
 
+LOSS_MAX_PREDICTIONS = 32
+RMD_LOSS_L1, RMD_LOSS_L2, RMD_LOSS_ABSMEAN, RMD_LOSS_ROBUST = 1, 2, 3, 4
+
+
+class LossPrediction(ctypes.Structure):
+    """Mirror of rmd_loss_prediction (include/rmd.h)."""
+
+    _fields_ = [
+        ("flow", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+        ("height", ctypes.c_int), ("width", ctypes.c_int), ("weight", ctypes.c_float),
+    ]
+
+
 class RmdError(RuntimeError):
     pass
 
@@ -94,6 +107,9 @@ _SIGS = {
     "rmd_up8_backward": (_I, [_P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P]),
     "rmd_softargmax": (_I, [_P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_softargmax_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
+    "rmd_sequence_loss_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
+    "rmd_sequence_loss": (_I, [_P, _I, _P, _P] + [_I] * 6 + [ctypes.c_float, _P, _P, _P, _P]),
+    "rmd_sequence_loss_backward": (_I, [_P, _I, _P, _P] + [_I] * 5 + [ctypes.c_float, _P, _P, _P]),
     "rmd_last_error": (ctypes.c_char_p, []),
     "rmd_version": (ctypes.c_char_p, []),
     "rmd_abi_version": (_I, []),

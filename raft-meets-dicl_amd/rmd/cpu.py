@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import LIB, _SCHEMAS, _STORAGE, pyramid_elements, pyramid_layout, pyramid_storage, s24_decode
+from .library import (LIB, _LOSS_SCHEMAS, _SCHEMAS, _STORAGE, check_loss_args, pyramid_elements, pyramid_layout,
+                      pyramid_storage, s24_decode)
 
 
 def _delta(r, device):
@@ -333,6 +334,78 @@ def softargmax_backward(grad, cost, levels, radius, temperature):
         return torch.autograd.grad(softargmax(c, levels, radius, temperature), c, grad.float())[0]
 
 
+# ---- sequence losses (raft.py:616-644, loss/mlseq.py:34-67, raft_dicl_ctf_l3.py:430-473, dicl.py:436-472) ----
+
+def loss_upsample(flow, shape, mode="bilinear"):
+    """mlseq.py:59-67 / raft_dicl_ctf_l3.py:465-473: interpolate, then scale each component by its ratio."""
+    _b, _c, fh, fw = flow.shape
+    th, tw = shape[-2:]
+    flow = F.interpolate(flow, (th, tw), mode=mode, align_corners=None if mode == "nearest" else True)
+    flow[:, 0, :, :] = flow[:, 0, :, :] * (tw / fw)
+    flow[:, 1, :, :] = flow[:, 1, :, :] * (th / fh)
+    return flow
+
+
+def sequence_loss_eager(flows, target, valid, masks, weights, ord, include_invalid, skip_empty, scale,
+                        mode="bilinear"):
+    """The reference's loop for any `ord` / upsampling mode -> (loss, per-prediction pixel counts)."""
+    target = target.float()
+    loss = target.new_zeros(())
+    counts = []
+    for flow, mask, weight in zip(flows, masks, weights):
+        flow = flow.float()
+        if flow.shape != target.shape:
+            flow = loss_upsample(flow, target.shape, mode)              # mlseq.py:45-46
+        if ord == "absmean":
+            dist = (flow - target).abs().mean(dim=-3)                   # raft.py:627-628
+        elif ord == "robust":
+            dist = ((flow - target).abs().sum(dim=-3) + 1e-8) ** 0.4    # dicl.py:450-451
+        else:
+            dist = torch.linalg.vector_norm(flow - target, ord=ord, dim=-3)     # raft.py:630, mlseq.py:49
+        mask = (valid if mask is None else mask).bool()
+        if include_invalid:
+            dist = dist * mask                                          # raft.py:633
+        else:
+            dist = dist[mask]                                           # raft.py:639, mlseq.py:52
+        counts.append(dist.numel())
+        if skip_empty and dist.numel() == 0:                            # raft_dicl_ctf_l3.py:453
+            continue
+        loss = loss + weight * dist.mean()                              # raft.py:642, mlseq.py:55
+    return loss * scale, torch.tensor(counts, dtype=torch.int64)        # mlseq.py:57
+
+
+_LOSS_ORD = {_lib.RMD_LOSS_L1: 1, _lib.RMD_LOSS_L2: 2, _lib.RMD_LOSS_ABSMEAN: "absmean", _lib.RMD_LOSS_ROBUST: "robust"}
+
+
+def sequence_loss(flows, target, valid, masks, mask_index, weights, norm, include_invalid, skip_empty, scale):
+    check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
+    own = [masks[i] if i >= 0 else None for i in mask_index]
+    return sequence_loss_eager(flows, target, valid, own, weights, _LOSS_ORD[norm], include_invalid, skip_empty, scale)
+
+
+def sequence_loss_backward(grad_loss, flows, target, valid, masks, mask_index, weights, counts, needs_grad, norm,
+                           include_invalid, scale):
+    with torch.enable_grad():
+        fl = [f.detach().float().requires_grad_(bool(need)) for f, need in zip(flows, needs_grad)]
+        # an empty selection contributes NaN to the loss but nothing to any gradient: skip it here
+        loss, _ = sequence_loss(fl, target.detach(), valid, masks, mask_index, weights, norm, include_invalid, True,
+                                scale)
+        wanted = [f for f, need in zip(fl, needs_grad) if need]
+        got = iter(torch.autograd.grad(loss, wanted, grad_loss.float().reshape(()), allow_unused=True)
+                   if wanted and loss.requires_grad else [None] * len(wanted))
+    out = []
+    for f, need in zip(fl, needs_grad):
+        if not need:
+            out.append(target.new_empty((0,)))
+            continue
+        g = next(got)
+        out.append(torch.zeros_like(f) if g is None else g)
+    return out
+
+
+_LOSS_KERNELS = {"sequence_loss": sequence_loss, "sequence_loss_backward": sequence_loss_backward}
+assert sorted(_LOSS_KERNELS) == sorted(_LOSS_SCHEMAS), "every rmd loss operator needs a CPU kernel"
+
 _KERNELS = {
     "corr_pyramid": corr_pyramid, "corr_lookup": corr_lookup,
     "corr_otf_prepare": corr_otf_prepare, "corr_otf_lookup": corr_otf_lookup,
@@ -345,6 +418,6 @@ _KERNELS = {
 }
 assert sorted(_KERNELS) == sorted(_SCHEMAS), "every rmd operator needs a CPU kernel"
 
-for _name, _fn in _KERNELS.items():
+for _name, _fn in list(_KERNELS.items()) + list(_LOSS_KERNELS.items()):
     LIB.impl(_name, _fn, "CPU")
     LIB.impl(_name, _fn, "AutogradCPU")

@@ -16,6 +16,8 @@ is again an rmd operator.  Schemas follow SURVEY.md §8(b):
   dap(x, weight)                                                             blocks/dicl.py:143-150
   up8(mask, flow, temperature), softargmax(cost, levels, radius, T)          raft.py:98-190, 319-331
   warp_backwards(img2, flow, eps) -> (est, mask)                             common/warp.py:5-33
+  sequence_loss(flows[], target, valid, masks[], ...) -> (loss, counts)      raft.py:616-644, loss/mlseq.py:34-67,
+        (the loss operators, listed by loss_operators())                     raft_dicl_ctf_l3.py:430-473, dicl.py:436-472
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -729,6 +731,140 @@ def _warp_bwd(ctx, grad, _gmask):
 torch.library.register_autograd("rmd::warp_backwards", _warp_bwd, setup_context=_warp_setup)
 
 
+# ---- sequence losses -----------------------------------------------------------------------------
+#
+# The loss operators take tensor lists (one entry per prediction).  They are kept in a table of their
+# own: _SCHEMAS / operators() is the SURVEY.md §8(b) model-operator set, loss_operators() lists these.
+# `masks` holds the distinct per-prediction masks and mask_index[k] the entry prediction k uses (-1:
+# the shared `valid`).  The list-valued autograd formula lives in rmd.ops (_SequenceLossFn).
+
+_LOSS_SCHEMAS = {
+    "sequence_loss": ("sequence_loss(Tensor[] flows, Tensor target, Tensor valid, Tensor[] masks, int[] mask_index, "
+                      "float[] weights, int norm, bool include_invalid, bool skip_empty, float scale) "
+                      "-> (Tensor, Tensor)"),
+    "sequence_loss_backward": ("sequence_loss_backward(Tensor grad_loss, Tensor[] flows, Tensor target, Tensor valid, "
+                               "Tensor[] masks, int[] mask_index, float[] weights, Tensor counts, bool[] needs_grad, "
+                               "int norm, bool include_invalid, float scale) -> Tensor[]"),
+}
+for _s in _LOSS_SCHEMAS.values():
+    LIB.define(_s)
+
+LOSS_NORMS = (_lib.RMD_LOSS_L1, _lib.RMD_LOSS_L2, _lib.RMD_LOSS_ABSMEAN, _lib.RMD_LOSS_ROBUST)
+
+
+def _u8(t):
+    """A (B, H, W) mask as contiguous bytes (bool is reinterpreted, not copied)."""
+    t = t.detach().contiguous()
+    if t.dtype == torch.bool:
+        return t.view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise ValueError(f"sequence_loss: masks must be bool or uint8, got {t.dtype}")
+    return t
+
+
+def check_loss_args(flows, target, valid, masks, mask_index, weights, norm):
+    """Shape and argument checks shared by the GPU, CPU and fake kernels of the loss operators."""
+    if target.dim() != 4 or target.shape[1] != 2:
+        raise ValueError(f"sequence_loss: target must be (B, 2, H, W), got {tuple(target.shape)}")
+    b, _, h, w = target.shape
+    if tuple(valid.shape) != (b, h, w):
+        raise ValueError(f"sequence_loss: valid must be (B, H, W) = ({b}, {h}, {w}), got {tuple(valid.shape)}")
+    if not flows or len(weights) != len(flows) or len(mask_index) != len(flows):
+        raise ValueError(f"sequence_loss: {len(flows)} flows, {len(weights)} weights, {len(mask_index)} mask indices")
+    if norm not in LOSS_NORMS:
+        raise ValueError(f"sequence_loss: norm {norm} (supported: RMD_LOSS_L1 = 1, RMD_LOSS_L2 = 2, "
+                         f"RMD_LOSS_ABSMEAN = 3, RMD_LOSS_ROBUST = 4)")
+    for f in flows:
+        if f.dim() != 4 or f.shape[0] != b or f.shape[1] != 2 or f.shape[2] < 1 or f.shape[3] < 1:
+            raise ValueError(f"sequence_loss: a prediction must be ({b}, 2, h, w), got {tuple(f.shape)}")
+    for m in masks:
+        if tuple(m.shape) != (b, h, w):
+            raise ValueError(f"sequence_loss: a mask must be ({b}, {h}, {w}), got {tuple(m.shape)}")
+    for i in mask_index:
+        if not -1 <= i < len(masks):
+            raise ValueError(f"sequence_loss: mask index {i} with {len(masks)} masks")
+
+
+def _all_gpu(name, *tensors):
+    for t in tensors:
+        if t.device.type != "cuda":
+            raise ValueError(f"rmd::{name}: all tensors must be on the GPU, got one on {t.device}")
+    _check_device(name, *tensors)
+
+
+def _loss_table(flows, masks, mask_index, weights, grads=None):
+    table = (_lib.LossPrediction * len(flows))()
+    for k, f in enumerate(flows):
+        e = table[k]
+        e.flow = f.data_ptr()
+        e.mask = masks[mask_index[k]].data_ptr() if mask_index[k] >= 0 else None
+        e.grad = grads[k].data_ptr() if grads is not None and grads[k] is not None else None
+        e.height, e.width = f.shape[2], f.shape[3]
+        e.weight = float(weights[k])
+    return table
+
+
+def _sequence_loss(flows, target, valid, masks, mask_index, weights, norm, include_invalid, skip_empty, scale):
+    check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
+    _all_gpu("sequence_loss", target, valid, *flows, *masks)
+    fl, tg, va, ms = [_f32(f) for f in flows], _f32(target), _u8(valid), [_u8(m) for m in masks]
+    b, _, h, w = tg.shape
+    lib = _lib.lib()
+    n = len(fl)
+    ws = torch.empty(lib.rmd_sequence_loss_workspace_bytes(b, h, w, min(n, _lib.LOSS_MAX_PREDICTIONS)),
+                     dtype=torch.uint8, device=tg.device)
+    loss = torch.empty((), dtype=torch.float32, device=tg.device)
+    counts = torch.empty((n,), dtype=torch.int64, device=tg.device)
+    table = _loss_table(fl, ms, mask_index, weights)
+    with _Dev(tg) as st:
+        _lib.check(lib.rmd_sequence_loss(table, n, _ptr(tg), _ptr(va), b, h, w, norm, int(include_invalid),
+                                         int(skip_empty), float(scale), _ptr(loss), _ptr(counts), _ptr(ws), st),
+                   "rmd_sequence_loss")
+    return loss, counts
+
+
+LIB.impl("sequence_loss", _sequence_loss, "CUDA")
+
+
+@_fake("sequence_loss")
+def _(flows, target, valid, masks, mask_index, weights, norm, include_invalid, skip_empty, scale):
+    check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
+    return (target.new_empty((), dtype=torch.float32), target.new_empty((len(flows),), dtype=torch.int64))
+
+
+def _sequence_loss_backward(grad_loss, flows, target, valid, masks, mask_index, weights, counts, needs_grad, norm,
+                            include_invalid, scale):
+    check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
+    _all_gpu("sequence_loss_backward", grad_loss, target, valid, counts, *flows, *masks)
+    if len(needs_grad) != len(flows) or counts.dtype != torch.int64 or counts.numel() != len(flows):
+        raise ValueError("sequence_loss_backward: needs_grad and counts (int64) must have one entry per prediction")
+    fl, tg, va, ms = [_f32(f) for f in flows], _f32(target), _u8(valid), [_u8(m) for m in masks]
+    g, cn = _f32(grad_loss).reshape(()), counts.contiguous()
+    b, _, h, w = tg.shape
+    # a prediction that needs no gradient gets none: a null pointer to the kernel, an empty tensor here
+    grads = [torch.empty_like(f) if need else None for f, need in zip(fl, needs_grad)]
+    if any(needs_grad):
+        table = _loss_table(fl, ms, mask_index, weights, grads)
+        with _Dev(tg) as st:
+            _lib.check(_lib.lib().rmd_sequence_loss_backward(table, len(fl), _ptr(tg), _ptr(va), b, h, w, norm,
+                                                             int(include_invalid), float(scale), _ptr(g), _ptr(cn),
+                                                             st), "rmd_sequence_loss_backward")
+    return [x if x is not None else tg.new_empty((0,)) for x in grads]
+
+
+LIB.impl("sequence_loss_backward", _sequence_loss_backward, "CUDA")
+
+
+@_fake("sequence_loss_backward")
+def _(grad_loss, flows, target, valid, masks, mask_index, weights, counts, needs_grad, norm, include_invalid, scale):
+    return [f.new_empty(f.shape if need else (0,), dtype=torch.float32) for f, need in zip(flows, needs_grad)]
+
+
 def operators():
-    """Names of the registered torch.ops.rmd operators."""
+    """Names of the registered torch.ops.rmd model operators."""
     return sorted(_SCHEMAS)
+
+
+def loss_operators():
+    """Names of the registered torch.ops.rmd loss operators."""
+    return sorted(_LOSS_SCHEMAS)

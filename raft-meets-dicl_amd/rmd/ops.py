@@ -501,3 +501,82 @@ def softargmax(cost, levels, radius, temperature=1.0):
     (torch.ops.rmd.softargmax; raft.py:112-135, corr/dot.py:83-90)."""
     _same_device(cost)
     return list(torch.ops.rmd.softargmax(cost, levels, radius, float(temperature)).unbind(0))
+
+
+# ---- sequence losses -----------------------------------------------------------------------------
+
+LOSS_ORDS = {1: _lib.RMD_LOSS_L1, 2: _lib.RMD_LOSS_L2, "absmean": _lib.RMD_LOSS_ABSMEAN,
+             "robust": _lib.RMD_LOSS_ROBUST}
+LOSS_MODES = ("bilinear",)
+
+
+class _SequenceLossFn(torch.autograd.Function):
+    """Autograd node of one rmd_sequence_loss call (a list-valued formula, like _CorrPyramidFn).  The
+    backward recomputes from the inputs: only the K pixel counts are kept besides them."""
+
+    @staticmethod
+    def forward(ctx, target, valid, masks, mask_index, weights, norm, include_invalid, skip_empty, scale, *flows):
+        loss, counts = torch.ops.rmd.sequence_loss(list(flows), target, valid, masks, mask_index, weights, norm,
+                                                   include_invalid, skip_empty, scale)
+        ctx.save_for_backward(target, valid, counts, *masks, *flows)
+        ctx.meta = (len(masks), mask_index, weights, norm, include_invalid, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        nmask, mask_index, weights, norm, include_invalid, scale = ctx.meta
+        target, valid, counts = ctx.saved_tensors[:3]
+        masks = list(ctx.saved_tensors[3:3 + nmask])
+        flows = list(ctx.saved_tensors[3 + nmask:])
+        needs = [bool(n) for n in ctx.needs_input_grad[9:]]
+        grads = torch.ops.rmd.sequence_loss_backward(gloss, flows, target, valid, masks, mask_index, weights, counts,
+                                                     needs, norm, include_invalid, scale)
+        return (None,) * 9 + tuple(g.to(f.dtype) if n else None for g, f, n in zip(grads, flows, needs))
+
+
+def sequence_loss(flows, target, valid, weights, ord=1, masks=None, include_invalid=False, skip_empty=False,
+                  scale=1.0, mode="bilinear"):
+    """scale * sum_k weights[k] * mean over the set pixels of dist_ord(up(flows[k]) - target) — the loop of
+    raft.py:616-644, loss/mlseq.py:34-57, raft_dicl_ctf_l3.py:430-463 and dicl.py:436-462 in one fused pass
+    (torch.ops.rmd.sequence_loss).  flows: (B, 2, h_k, w_k) each, upsampled bilinearly (align_corners, scaled
+    by the size ratios) where smaller than target (B, 2, H, W); valid (B, H, W) bool or uint8; masks: None or
+    one entry per prediction, a (B, H, W) mask that replaces `valid` or None.  GPU tensors run the HIP
+    kernels and never fall back: ord must be 1, 2, 'absmean' or 'robust' and mode 'bilinear'."""
+    flows = list(flows)
+    masks = [None] * len(flows) if masks is None else list(masks)
+    weights = [float(w) for w in weights]
+    if len(masks) != len(flows) or len(weights) != len(flows):
+        raise ValueError(f"sequence_loss: {len(flows)} flows, {len(weights)} weights, {len(masks)} masks")
+    _same_device(target, valid, *flows, *[m for m in masks if m is not None])
+    try:
+        norm = LOSS_ORDS.get(ord)
+    except TypeError:
+        norm = None
+    if norm is None or mode not in LOSS_MODES:
+        if target.device.type != "cpu":
+            raise ValueError(f"sequence_loss: ord={ord!r}, mode={mode!r} has no HIP kernel (supported: ord 1, 2, "
+                             f"'absmean', 'robust'; mode 'bilinear'); GPU tensors do not fall back")
+        from . import cpu
+        return cpu.sequence_loss_eager(flows, target, valid, masks, weights, ord, include_invalid, skip_empty,
+                                       scale, mode)[0]
+    total = None
+    step = _lib.LOSS_MAX_PREDICTIONS
+    for i in range(0, len(flows), step):
+        own, index = [], []
+        for m in masks[i:i + step]:
+            if m is None:
+                index.append(-1)
+            else:
+                hit = next((j for j, o in enumerate(own) if o is m), None)
+                if hit is None:
+                    hit = len(own)
+                    own.append(m)
+                index.append(hit)
+        if target.device.type == "cpu":        # the CPU kernel's own ATen graph carries the gradient
+            part = torch.ops.rmd.sequence_loss(flows[i:i + step], target, valid, own, index, weights[i:i + step],
+                                               norm, include_invalid, skip_empty, float(scale))[0]
+        else:
+            part = _SequenceLossFn.apply(target, valid, own, index, weights[i:i + step], norm, bool(include_invalid),
+                                         bool(skip_empty), float(scale), *flows[i:i + step])
+        total = part if total is None else total + part
+    return target.new_zeros((), dtype=torch.float32) if total is None else total
