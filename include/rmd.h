@@ -493,6 +493,50 @@ int rmd_sequence_loss_backward(const rmd_loss_prediction* preds, int npred, cons
                                int include_invalid, float scale, const float* grad_loss, const long long* counts,
                                void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Flow metrics (what an evaluation or training loop computes next from the same three tensors).
+ * One operation covers the reference's flow metrics, for every estimate of a call and every sample
+ * of the batch on its own (the evaluator's per-sample loop, src/evaluation/evaluator.py:29-37):
+ *   epe             EndPointError.compute, src/metrics/epe.py:35-53
+ *   fl-all          FlAll.compute, src/metrics/fl_all.py:29-44
+ *   aae             AverageAngularError.compute, src/metrics/aae.py:30-44
+ *   flow-magnitude  FlowMagnitude.compute, src/metrics/flow.py:32-36
+ * `estimates` is a HOST array of nest device pointers, each (B, 2, H, W) float32; target (B, 2, H, W)
+ * float32; valid (B, H, W) bytes (non-zero = set); `distances` a HOST array of nd floats.  The result
+ * is RAW statistics, stats (nest, B, RMD_METRICS_SLOTS) float64 — the caller divides:
+ *   slot 0       H*W
+ *   slot 1       number of set mask bytes of the sample
+ *   slot 2       sum over the set pixels of epe = sqrtf(d0*d0 + d1*d1), d = estimate - target, each
+ *                operation rounded in fp32 (epe.py:39), the sum in double
+ *   slot 3       number of set pixels with epe > fl_abs && epe > fl_rel * |target|_2, both norms and the
+ *                product in fp32 (fl_all.py:33-41; the reference's constants are 3 and 0.05f)
+ *   slot 4, 5    sum of the angle in radians over all pixels / over the set pixels:
+ *                acos(clamp((u u' + v v' + 1) / (|est| |tgt| + 1), -1, 1)) (aae.py:35-44) with u, v the
+ *                components 0, 1 of the CHANNEL axis, evaluated in double from the fp32 inputs; the clamp
+ *                keeps NaN as torch.clamp does
+ *   slot 6       sum over all pixels of |estimate|_ord in fp32 (flow.py:34), mag_ord = 1, 2, +inf or any
+ *                other p > 0 (anything else: RMD_ERR_ARG)
+ *   slot 7       number of pixels with a non-finite estimate component
+ *   slot 8 + i   number of set pixels with epe <= distances[i], i < nd <= RMD_METRICS_MAX_DISTANCES
+ *                (epe.py:51); slots past 8 + nd are 0
+ * Sums are double and carry NaN / Inf; counts are integers, exact; a comparison with NaN is false.  A
+ * pixel outside the mask reaches slots 0, 4, 6 and 7 of its own sample only, and no sample reaches
+ * another sample's row.  No set pixel is not special: the caller's division gives NaN as mean() of an
+ * empty tensor does.  Blocks write partial rows to `workspace` (rmd_flow_metrics_workspace_bytes()
+ * bytes) with plain stores and a second kernel adds them in block order: no atomics, bitwise
+ * reproducible, and an estimate's rows do not depend on the other estimates of the call.  At most
+ * RMD_METRICS_MAX_ESTIMATES per call (the table is a kernel argument); a caller chunks longer lists.
+ * All argument checks run on the host before any launch.
+ */
+#define RMD_METRICS_MAX_ESTIMATES 32
+#define RMD_METRICS_MAX_DISTANCES 8
+#define RMD_METRICS_SLOTS 16
+
+size_t rmd_flow_metrics_workspace_bytes(int batch, int height, int width, int nest);
+int rmd_flow_metrics(const float* const* estimates, int nest, const float* target, const unsigned char* valid,
+                     int batch, int height, int width, const float* distances, int nd, float fl_abs, float fl_rel,
+                     float mag_ord, double* stats, void* workspace, void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

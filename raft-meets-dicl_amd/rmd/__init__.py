@@ -17,10 +17,14 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
   rmd.loss.SequenceLoss / MultiLevelSequenceLoss / RestrictedMultiLevelSequenceLoss / MultiscaleLoss
                                         <- raft.py:596-644, common/loss/mlseq.py, raft_dicl_ctf_l3.py:401-473,
                                            dicl.py:416-472 (one fused forward + backward, rmd.ops.sequence_loss)
+  rmd.metrics.EndPointError / FlAll / AverageAngularError / FlowMagnitude / Loss / FlowMetrics
+                                        <- src/metrics/{epe,fl_all,aae,flow,loss}.py, src/cmd/eval.py:93-109
+                                           (one fused statistics pass, rmd.ops.flow_metrics)
 """
 
-from . import blocks, config, corr, cpu, dicl, heads, input, loss, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
+from . import blocks, config, corr, cpu, dicl, heads, input, loss, metrics, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
 from .loss import MultiLevelSequenceLoss, MultiscaleLoss, RestrictedMultiLevelSequenceLoss, SequenceLoss  # noqa: F401
+from .metrics import FlowMetrics  # noqa: F401
 from .ops import set_default_precision, get_default_precision  # noqa: F401
 
 __version__ = "0.1"

@@ -48,6 +48,9 @@ class LossPrediction(ctypes.Structure):
     ]
 
 
+METRICS_MAX_ESTIMATES, METRICS_MAX_DISTANCES, METRICS_SLOTS = 32, 8, 16
+
+
 class RmdError(RuntimeError):
     pass
 
@@ -110,6 +113,9 @@ _SIGS = {
     "rmd_sequence_loss_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
     "rmd_sequence_loss": (_I, [_P, _I, _P, _P] + [_I] * 6 + [ctypes.c_float, _P, _P, _P, _P]),
     "rmd_sequence_loss_backward": (_I, [_P, _I, _P, _P] + [_I] * 5 + [ctypes.c_float, _P, _P, _P]),
+    "rmd_flow_metrics_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
+    "rmd_flow_metrics": (_I, [ctypes.POINTER(_P), _I, _P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_float), _I]
+                         + [ctypes.c_float] * 3 + [_P, _P, _P]),
     "rmd_last_error": (ctypes.c_char_p, []),
     "rmd_version": (ctypes.c_char_p, []),
     "rmd_abi_version": (_I, []),

@@ -21,8 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _LOSS_SCHEMAS, _SCHEMAS, _STORAGE, check_loss_args, pyramid_elements, pyramid_layout,
-                      pyramid_storage, s24_decode)
+from .library import (LIB, _LOSS_SCHEMAS, _METRIC_SCHEMAS, _SCHEMAS, _STORAGE, check_loss_args, check_metric_args,
+                      pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
 def _delta(r, device):
@@ -405,6 +405,69 @@ def sequence_loss_backward(grad_loss, flows, target, valid, masks, mask_index, w
 
 _LOSS_KERNELS = {"sequence_loss": sequence_loss, "sequence_loss_backward": sequence_loss_backward}
 assert sorted(_LOSS_KERNELS) == sorted(_LOSS_SCHEMAS), "every rmd loss operator needs a CPU kernel"
+
+# ---- flow metrics (metrics/epe.py:35-53, fl_all.py:29-44, aae.py:30-44, flow.py:32-36) ------------
+
+def metric_angle(estimate, target):
+    """aae.py:32-44 per pixel in radians, on the CHANNEL axis (dim -3) and in float64 from the inputs as
+    they are: what the reference evaluates when it is handed channel-last views."""
+    u_est, v_est = estimate.double().unbind(-3)
+    u_tgt, v_tgt = target.double().unbind(-3)
+    n_est = torch.sqrt(torch.square(u_est) + torch.square(v_est))
+    n_tgt = torch.sqrt(torch.square(u_tgt) + torch.square(v_tgt))
+    cos = (u_est * u_tgt + v_est * v_tgt + 1) / (n_est * n_tgt + 1)
+    return torch.arccos(torch.clamp(cos, -1.0, 1.0))
+
+
+def flow_metrics_eager(estimate, target, valid, distances=(1, 3, 5), fl=(3, 0.05), ord=2):
+    """The reference's expressions one metric after the other, boolean indexing included (each
+    `epe[valid]` launches nonzero and waits for the host on a GPU) -> dict of 0-dim tensors.  A batch
+    or a single instance, like the reference's classes."""
+    out = {}
+    epe = torch.linalg.vector_norm(estimate - target, ord=2, dim=-3)[valid]         # epe.py:39-42
+    out["epe/mean"] = epe.mean()
+    for d in distances:
+        out[f"epe/{d}px"] = (epe <= d).float().mean()                               # epe.py:51
+    epe = torch.linalg.vector_norm(estimate - target, ord=2, dim=-3)[valid]         # fl_all.py:33-38
+    tgt = torch.linalg.vector_norm(target, ord=2, dim=-3)[valid]
+    out["fl-all"] = torch.logical_and(epe > fl[0], epe > fl[1] * tgt).float().mean()     # fl_all.py:41-44
+    out["aae"] = torch.rad2deg(metric_angle(estimate, target).mean())               # aae.py:44
+    out["flow-magnitude"] = torch.linalg.vector_norm(estimate, ord=ord, dim=-3).mean()   # flow.py:34
+    return out
+
+
+def flow_metrics(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
+    """The slot table of include/rmd.h from the same expressions, every sample on its own: selections
+    (`where`), never products, so a NaN outside the mask stays out of the masked sums."""
+    check_metric_args(estimates, target, valid, distances, mag_ord)
+    target = target.detach().float()
+    mask = valid.detach() != 0
+    b, _, h, w = target.shape
+    tgt = torch.linalg.vector_norm(target, ord=2, dim=-3)
+    zero = target.new_zeros((), dtype=torch.float64)
+
+    def total(x, where=None):
+        x = x.double()
+        return (x if where is None else torch.where(where, x, zero)).sum(dim=(-2, -1))
+
+    rows = []
+    for est in estimates:
+        est = est.detach().float()
+        epe = torch.linalg.vector_norm(est - target, ord=2, dim=-3)
+        ang = metric_angle(est, target)
+        slots = [torch.full((b,), float(h * w), dtype=torch.float64, device=target.device), total(mask),
+                 total(epe, mask), total((epe > fl_abs) & (epe > fl_rel * tgt) & mask), total(ang), total(ang, mask),
+                 total(torch.linalg.vector_norm(est, ord=mag_ord, dim=-3)), total((~torch.isfinite(est)).any(dim=-3))]
+        slots += [total((epe <= d) & mask) for d in distances]
+        slots += [zero.expand(b)] * (_lib.METRICS_SLOTS - len(slots))
+        rows.append(torch.stack(slots, dim=-1))
+    return torch.stack(rows)
+
+
+_METRIC_KERNELS = {"flow_metrics": flow_metrics}
+assert sorted(_METRIC_KERNELS) == sorted(_METRIC_SCHEMAS), "every rmd metric operator needs a CPU kernel"
+for _name, _fn in _METRIC_KERNELS.items():
+    LIB.impl(_name, _fn, "CPU")         # not differentiable: library.py's Autograd kernel serves every device
 
 _KERNELS = {
     "corr_pyramid": corr_pyramid, "corr_lookup": corr_lookup,

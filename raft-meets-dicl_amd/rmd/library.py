@@ -860,6 +860,75 @@ def _(grad_loss, flows, target, valid, masks, mask_index, weights, counts, needs
     return [f.new_empty(f.shape if need else (0,), dtype=torch.float32) for f, need in zip(flows, needs_grad)]
 
 
+# ---- flow metrics --------------------------------------------------------------------------------
+#
+# A third table: metric_operators().  The operator returns the raw statistics of include/rmd.h
+# (estimates, samples, RMD_METRICS_SLOTS) float64; rmd.ops.flow_metrics derives the metrics from them.
+# It is not differentiable: its Autograd kernel runs the backend kernel below autograd, so the
+# result never carries a graph.
+
+_METRIC_SCHEMAS = {
+    "flow_metrics": ("flow_metrics(Tensor[] estimates, Tensor target, Tensor valid, float[] distances, float fl_abs, "
+                     "float fl_rel, float mag_ord) -> Tensor"),
+}
+for _s in _METRIC_SCHEMAS.values():
+    LIB.define(_s)
+
+
+def check_metric_args(estimates, target, valid, distances, mag_ord):
+    """Shape and argument checks shared by the GPU, CPU and fake kernels of flow_metrics."""
+    if target.dim() != 4 or target.shape[1] != 2:
+        raise ValueError(f"flow_metrics: target must be (B, 2, H, W), got {tuple(target.shape)}")
+    b, _, h, w = target.shape
+    if tuple(valid.shape) != (b, h, w):
+        raise ValueError(f"flow_metrics: valid must be (B, H, W) = ({b}, {h}, {w}), got {tuple(valid.shape)}")
+    if not 1 <= len(estimates) <= _lib.METRICS_MAX_ESTIMATES:
+        raise ValueError(f"flow_metrics: {len(estimates)} estimates (1..{_lib.METRICS_MAX_ESTIMATES} per call; "
+                         f"rmd.ops.flow_metrics chunks longer lists)")
+    if len(distances) > _lib.METRICS_MAX_DISTANCES:
+        raise ValueError(f"flow_metrics: {len(distances)} distances (0..{_lib.METRICS_MAX_DISTANCES} per call; "
+                         f"rmd.ops.flow_metrics chunks longer lists)")
+    if not mag_ord > 0:
+        raise ValueError(f"flow_metrics: bad mag_ord {mag_ord} (1, 2, inf or any other p > 0)")
+    for e in estimates:
+        if tuple(e.shape) != tuple(target.shape):
+            raise ValueError(f"flow_metrics: an estimate must be {tuple(target.shape)}, got {tuple(e.shape)}")
+
+
+def _flow_metrics(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
+    check_metric_args(estimates, target, valid, distances, mag_ord)
+    _all_gpu("flow_metrics", target, valid, *estimates)
+    es, tg, va = [_f32(e) for e in estimates], _f32(target), _u8(valid)
+    b, _, h, w = tg.shape
+    lib = _lib.lib()
+    n, nd = len(es), len(distances)
+    ws = torch.empty(lib.rmd_flow_metrics_workspace_bytes(b, h, w, n), dtype=torch.uint8, device=tg.device)
+    stats = torch.empty((n, b, _lib.METRICS_SLOTS), dtype=torch.float64, device=tg.device)
+    table = (ctypes.c_void_p * n)(*[e.data_ptr() for e in es])
+    dist = (ctypes.c_float * max(nd, 1))(*[float(d) for d in distances])
+    with _Dev(tg) as st:
+        _lib.check(lib.rmd_flow_metrics(table, n, _ptr(tg), _ptr(va), b, h, w, dist, nd, float(fl_abs), float(fl_rel),
+                                        float(mag_ord), _ptr(stats), _ptr(ws), st), "rmd_flow_metrics")
+    return stats
+
+
+LIB.impl("flow_metrics", _flow_metrics, "CUDA")
+
+
+@_fake("flow_metrics")
+def _(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
+    check_metric_args(estimates, target, valid, distances, mag_ord)
+    return target.new_empty((len(estimates), target.shape[0], _lib.METRICS_SLOTS), dtype=torch.float64)
+
+
+def _flow_metrics_below_autograd(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.rmd.flow_metrics(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord)
+
+
+LIB.impl("flow_metrics", _flow_metrics_below_autograd, "Autograd")
+
+
 def operators():
     """Names of the registered torch.ops.rmd model operators."""
     return sorted(_SCHEMAS)
@@ -868,3 +937,8 @@ def operators():
 def loss_operators():
     """Names of the registered torch.ops.rmd loss operators."""
     return sorted(_LOSS_SCHEMAS)
+
+
+def metric_operators():
+    """Names of the registered torch.ops.rmd metric operators."""
+    return sorted(_METRIC_SCHEMAS)

@@ -580,3 +580,110 @@ def sequence_loss(flows, target, valid, weights, ord=1, masks=None, include_inva
                                          bool(skip_empty), float(scale), *flows[i:i + step])
         total = part if total is None else total + part
     return target.new_zeros((), dtype=torch.float32) if total is None else total
+
+
+# ---- flow metrics --------------------------------------------------------------------------------
+
+_SLOT_PIXELS, _SLOT_VALID, _SLOT_EPE, _SLOT_FL, _SLOT_ANGLE, _SLOT_ANGLE_VALID, _SLOT_MAG, _SLOT_BAD, _SLOT_NEAR = range(9)
+
+
+class FlowMetricsResult:
+    """Raw statistics of one rmd.ops.flow_metrics call: `stats` (estimates, samples, 8 + len(distances))
+    float64 on the inputs' device, slots as in include/rmd.h (the 8 fixed ones, then one count per
+    distance).  per_sample() / batch() derive the metrics as tensors on that device; nothing is read
+    back before host(), which copies everything to the CPU in one transfer."""
+
+    def __init__(self, stats, distances, ord, extra=None):
+        self.stats = stats
+        self.distances = tuple(distances)
+        self.ord = ord
+        self.extra = extra
+        self._derived = {}              # per_sample() / batch() are derived once; `stats` is not modified
+
+    def _derive(self, s):
+        n_px, n_valid = s[..., _SLOT_PIXELS], s[..., _SLOT_VALID]
+        return {
+            "n_pixels": n_px, "n_valid": n_valid, "nonfinite": s[..., _SLOT_BAD],
+            "epe": s[..., _SLOT_EPE] / n_valid,                                     # epe.py:50
+            "within": s[..., _SLOT_NEAR:] / n_valid.unsqueeze(-1),                  # epe.py:51, one per distance
+            "fl_all": s[..., _SLOT_FL] / n_valid,                                   # fl_all.py:44
+            "aae": torch.rad2deg(s[..., _SLOT_ANGLE] / n_px),                       # aae.py:44, all pixels
+            "aae_valid": torch.rad2deg(s[..., _SLOT_ANGLE_VALID] / n_valid),
+            "magnitude": s[..., _SLOT_MAG] / n_px,                                  # flow.py:34
+        }
+
+    def per_sample(self):
+        """Every sample on its own: tensors (estimates, samples), `within` (estimates, samples, distances)."""
+        if "per_sample" not in self._derived:
+            self._derived["per_sample"] = self._derive(self.stats)
+        return self._derived["per_sample"]
+
+    def batch_stats(self):
+        """The sample rows added in index order (estimates, slots)."""
+        total = self.stats[:, 0]
+        for b in range(1, self.stats.shape[1]):
+            total = total + self.stats[:, b]
+        return total
+
+    def batch(self):
+        """The whole batch as one set of pixels: tensors (estimates,), `within` (estimates, distances)."""
+        if "batch" not in self._derived:
+            self._derived["batch"] = self._derive(self.batch_stats())
+        return self._derived["batch"]
+
+    def host(self):
+        """The same result on the CPU: ONE device-to-host copy carries the statistics and `extra` (a
+        tensor that rides along, e.g. the loss; returned as float64 in `.extra`)."""
+        if self.stats.device.type == "cpu":
+            extra = None if self.extra is None else self.extra.detach().double()
+            return FlowMetricsResult(self.stats, self.distances, self.ord, extra)
+        if self.extra is None:
+            return FlowMetricsResult(self.stats.cpu(), self.distances, self.ord)
+        extra = self.extra.detach()
+        packed = torch.cat([self.stats.reshape(-1), extra.double().reshape(-1)]).cpu()
+        n = self.stats.numel()
+        return FlowMetricsResult(packed[:n].view(self.stats.shape), self.distances, self.ord,
+                                 packed[n:].view(extra.shape))
+
+
+def _widen(t):
+    """fp16 / bf16 (anything but fp32) widened, contiguous, detached."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t.contiguous()
+
+
+def flow_metrics(estimates, target, valid, distances=(1, 3, 5), fl=(3, 0.05), ord=2, extra=None):
+    """The flow metrics of src/metrics (epe.py, fl_all.py, aae.py, flow.py) for every estimate and every
+    sample in one fused pass (torch.ops.rmd.flow_metrics) -> FlowMetricsResult.  estimates: one tensor or
+    a sequence, each shaped like target: (B, 2, H, W) or a single instance (2, H, W) (then valid is
+    (H, W) and B = 1); valid bool or uint8.  distances: the epe thresholds (`<=`), fl: (absolute,
+    relative) outlier thresholds, ord: the magnitude's norm (1, 2, inf or any other p > 0).  More than 8
+    distances or 32 estimates are chunked into several launches.  Nothing synchronises with the host:
+    read the result with .host().  Not differentiable."""
+    estimates = [estimates] if isinstance(estimates, torch.Tensor) else list(estimates)
+    if not estimates:
+        raise ValueError("flow_metrics: no estimate")
+    _same_device(target, valid, *estimates)
+    if target.dim() == 3:
+        target, valid = target.unsqueeze(0), valid.unsqueeze(0)
+        estimates = [e.unsqueeze(0) if e.dim() == 3 else e for e in estimates]
+    if valid.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"flow_metrics: valid must be bool or uint8, got {valid.dtype}")
+    ord = float(ord)
+    if not ord > 0:
+        raise ValueError(f"flow_metrics: bad ord {ord} (1, 2, inf or any other p > 0)")
+    distances = [float(d) for d in distances]
+    es, tg, va = [_widen(e) for e in estimates], _widen(target), valid.detach().contiguous()
+    dstep, estep = _lib.METRICS_MAX_DISTANCES, _lib.METRICS_MAX_ESTIMATES
+    rows = []
+    for i in range(0, len(es), estep):
+        parts = []
+        for j in range(0, max(len(distances), 1), dstep):
+            chunk = distances[j:j + dstep]
+            st = torch.ops.rmd.flow_metrics(es[i:i + estep], tg, va, chunk, float(fl[0]), float(fl[1]), ord)
+            parts.append(st[..., :_SLOT_NEAR + len(chunk)] if j == 0 else st[..., _SLOT_NEAR:_SLOT_NEAR + len(chunk)])
+        rows.append(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
+    stats = rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)
+    return FlowMetricsResult(stats, distances, ord, extra)
