@@ -301,6 +301,22 @@ int rmd_dicl_stack_backward(const float* grad_stack, const float* coords, int ba
                             int level, int norm_height, int norm_width, int extra_delta,
                             float* grad_fmap1, float* grad_fmap2, void* stream);
 
+/*
+ * Name of the kernel rmd_dicl_stack (backward = 0) or rmd_dicl_stack_backward (backward = 1) runs for
+ * these arguments: the launchers dispatch on the same decision.  Host only, no GPU call; the string
+ * is static.  Forward: "patch/R" (unit steps, R = 1..4), "separable/R/K" (scaled grid, R = 3, 4,
+ * K x K patch, K = 4, 6, 8), "general".  Backward: "patch2/R/small|large" and "patch1/R/small|large"
+ * (unit steps, two pixels or one per lane; one only for stacks of >= 4 GiB per image),
+ * "separable2/K/small|large" (K = 4, 6, 8), "separable1/10/small|large", "general/small|large" and
+ * "fallback"; small / large is the LDS window, 16 or 48 KiB.  "invalid" for arguments the calls reject.
+ * rmd_dicl_stack_kernel_list: every kernel name the query can return for that direction,
+ * comma-separated ("invalid" names no kernel and is not listed).
+ */
+const char* rmd_dicl_stack_kernel(int batch, int channels, int height, int width, int level_height,
+                                  int level_width, int radius, int level, int norm_height, int norm_width,
+                                  int extra_delta, int backward);
+const char* rmd_dicl_stack_kernel_list(int backward);
+
 /* Bytes of device workspace rmd_dicl_stack_int(_backward) needs (occlusion mask, 1 B/pixel). */
 size_t rmd_dicl_stack_int_workspace_bytes(int batch, int height, int width);
 

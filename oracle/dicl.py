@@ -21,6 +21,13 @@ import numpy as np
 from .corr import _sample_features
 
 
+def _grid_scale(hl, wl, nh, nw):
+    """(w_i-1)/(w-1), (h_i-1)/(h-1) as IEEE division: a 1-pixel normalisation map gives inf (or NaN for
+    0/0) as the reference's tensor arithmetic does, where Python's `/` raises ZeroDivisionError."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (np.float64(wl - 1) / np.float64(nw - 1), np.float64(hl - 1) / np.float64(nh - 1))
+
+
 def dicl_stack(f1, f2, coords, radius, level=0, norm_hw=None):
     """(B,C,h,w) f1, (B,C,h_i,w_i) f2, coords (B,2,h,w) -> stack (B, d, d, 2C, h, w)."""
     b, c, h, w = f1.shape
@@ -30,8 +37,7 @@ def dicl_stack(f1, f2, coords, radius, level=0, norm_hw=None):
     s = 2.0 ** level
     cx = coords[:, 0].reshape(b, h * w) / s
     cy = coords[:, 1].reshape(b, h * w) / s
-    sx = (wl - 1) / (nw - 1)
-    sy = (hl - 1) / (nh - 1)
+    sx, sy = _grid_scale(hl, wl, nh, nw)
     samp = _sample_features(f2, cx, cy, radius, sx, sy)                    # (B,C,P,a,b)
     samp = samp.reshape(b, c, h, w, d, d).transpose(0, 4, 5, 1, 2, 3)     # (B,a,b,C,h,w)
     f1e = np.broadcast_to(f1[:, None, None], (b, d, d, c, h, w))
@@ -48,8 +54,7 @@ def dicl_stack_backward(f2_shape, coords, radius, grad_stack, level=0, norm_hw=N
     gf1 = grad_stack[:, :, :, :c].sum(axis=(1, 2))
     gf2 = np.zeros((b, c, hl, wl), dtype=dt)
     s = 2.0 ** level
-    sx = (wl - 1) / (nw - 1)
-    sy = (hl - 1) / (nh - 1)
+    sx, sy = _grid_scale(hl, wl, nh, nw)
     cx = coords[:, 0] / s
     cy = coords[:, 1] / s
     bi = np.arange(b)[:, None, None]
@@ -58,6 +63,10 @@ def dicl_stack_backward(f2_shape, coords, radius, grad_stack, level=0, norm_hw=N
         for bb in range(d):
             px = (cx + (a - radius)) * sx
             py = (cy + (bb - radius)) * sy
+            # a non-finite position has no tap inside the map: it contributes nothing (ATen's
+            # grid_sampler_2d_backward adds only within-bounds taps), so NaN weights must not reach gf2
+            fin = np.isfinite(px) & np.isfinite(py)
+            px, py = np.where(fin, px, -2.0), np.where(fin, py, -2.0)
             x0 = np.floor(px)
             y0 = np.floor(py)
             fx, fy = px - x0, py - y0
@@ -124,8 +133,7 @@ def dicl_stack_at(f1, f2, coords, radius, idx, level=0, norm_hw=None):
     hl, wl = f2.shape[-2:]
     nh, nw = norm_hw if norm_hw is not None else (h, w)
     s = 2.0 ** level
-    sx = (wl - 1) / (nw - 1)
-    sy = (hl - 1) / (nh - 1)
+    sx, sy = _grid_scale(hl, wl, nh, nw)
     px = (coords[b, 0, y, x] / s + (a - radius)) * sx
     py = (coords[b, 1, y, x] / s + (bb - radius)) * sy
     x0, y0 = np.floor(px), np.floor(py)

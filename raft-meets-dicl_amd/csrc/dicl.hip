@@ -19,6 +19,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <string>
+#include <vector>
 
 namespace rmd {
 namespace {
@@ -46,6 +48,22 @@ __device__ __forceinline__ Taps make_taps(float px, float py, int hl, int wl) {
         const float wy = (k >> 1) ? fy : 1.f - fy;
         t.idx[k] = ok ? yy * wl + xx : 0;
         t.wgt[k] = ok ? wx * wy : 0.f;
+    }
+    return t;
+}
+
+// Forward only: a sample position that is not finite (a NaN or +-inf coordinate, a non-finite grid
+// scale) samples NaN, as the reference's grid_sample does; make_taps alone clamps it far outside the
+// map (fmaxf drops a NaN) and would sample zeros.  The backward keeps make_taps: such a position has
+// no tap inside the map and contributes nothing to grad_fmap2.
+__device__ __forceinline__ Taps make_taps_fwd(float px, float py, int hl, int wl) {
+    Taps t = make_taps(px, py, hl, wl);
+    if (!(__builtin_isfinite(px) && __builtin_isfinite(py))) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            t.idx[k] = 0;
+            t.wgt[k] = __builtin_nanf("");
+        }
     }
     return t;
 }
@@ -90,7 +108,7 @@ dicl_stack_kernel(const float* __restrict__ f1, const float* __restrict__ f2, co
         const int p = p0 + k;
         const float px = (cx[p] * P.inv_scale + (float)(a - P.radius)) * P.sx;
         const float py = (cy[p] * P.inv_scale + (float)(bb - P.radius)) * P.sy;
-        t[k] = make_taps(px, py, P.hl, P.wl);
+        t[k] = make_taps_fwd(px, py, P.hl, P.wl);
     }
     float* o = out + ((size_t)(b * d * d + disp) * C2) * n + p0;
     const float* f1b = f1 + (size_t)b * C * n + p0;
@@ -140,8 +158,12 @@ dicl_stack_sep_kernel(const float* __restrict__ f1, const float* __restrict__ f2
     const int p = blockIdx.x * kThreads + threadIdx.x;
     const int c = blockIdx.y, b = blockIdx.z;
     if (p >= n) return;
-    const float cxs = fminf(fmaxf(coords[(size_t)b * 2 * n + p] * P.inv_scale, -1.0e6f), 1.0e6f);
-    const float cys = fminf(fmaxf(coords[(size_t)b * 2 * n + n + p] * P.inv_scale, -1.0e6f), 1.0e6f);
+    const float cxr = coords[(size_t)b * 2 * n + p] * P.inv_scale, cyr = coords[(size_t)b * 2 * n + n + p] * P.inv_scale;
+    // a NaN or +-inf coordinate: the pixel's whole window is NaN (grid_sample); the clamp below would
+    // turn it into a far-away finite one (fmaxf drops a NaN) and the window into zeros
+    const bool finite = __builtin_isfinite(cxr) && __builtin_isfinite(cyr);
+    const float cxs = fminf(fmaxf(cxr, -1.0e6f), 1.0e6f);
+    const float cys = fminf(fmaxf(cyr, -1.0e6f), 1.0e6f);
     const int xbase = (int)floorf((cxs - (float)R) * P.sx), ybase = (int)floorf((cys - (float)R) * P.sy);
     int rx[D], ry[D];
     float fxa[D], fyb[D];
@@ -166,6 +188,7 @@ dicl_stack_sep_kernel(const float* __restrict__ f1, const float* __restrict__ f2
     const float* f2c = f2 + ((size_t)b * C + c) * nl;
     auto put = [&](int a, int bb, float v) {
         char* od = reinterpret_cast<char*>(ob + (size_t)(a * D + bb) * dstride);
+        v = finite ? v : __builtin_nanf("");
         if constexpr (NT) {
             __builtin_nontemporal_store(v1, reinterpret_cast<float*>(od + lo1));
             __builtin_nontemporal_store(v, reinterpret_cast<float*>(od + lo2));
@@ -319,11 +342,15 @@ dicl_stack_patch_kernel(const float* __restrict__ f1, const float* __restrict__ 
     for (int k = 0; k < PX; ++k) {
         float cx = coords[(size_t)b * 2 * n + p0 + k] * P.inv_scale;
         float cy = coords[(size_t)b * 2 * n + n + p0 + k] * P.inv_scale;
+        // a NaN or +-inf coordinate: NaN weights make the pixel's whole window NaN (grid_sample), at no
+        // cost in the store loop; the clamp alone turns it into a far-away finite coordinate (fmaxf
+        // drops a NaN) and the window into zeros
+        const bool finite = __builtin_isfinite(cx) && __builtin_isfinite(cy);
         cx = fminf(fmaxf(cx, -1.0e6f), 1.0e6f);
         cy = fminf(fmaxf(cy, -1.0e6f), 1.0e6f);
         const float fx0 = floorf(cx), fy0 = floorf(cy);
-        fx[k] = cx - fx0;
-        fy[k] = cy - fy0;
+        fx[k] = finite ? cx - fx0 : __builtin_nanf("");
+        fy[k] = finite ? cy - fy0 : __builtin_nanf("");
         xs[k] = (int)fx0 - R;
         ys[k] = (int)fy0 - R;
     }
@@ -1403,6 +1430,140 @@ int stack_params(StackParams& P, int B, int C, int h, int w, int hl, int wl, int
     return RMD_OK;
 }
 
+// ---- kernel routing ------------------------------------------------------------------------------
+// Which kernel a stack call runs: decided here, once, for the launchers and for the
+// rmd_dicl_stack_kernel query alike (host only, no GPU call).
+constexpr double kImageBytesMax = 4294967296.0;   // 32-bit lane offsets inside one image's stack
+
+double stack_image_bytes(const StackParams& P) {
+    const int d = 2 * P.radius + 1;
+    return 4.0 * d * d * (2.0 * P.C + P.extra) * P.h * P.w;
+}
+
+bool scale_in_01(const StackParams& P) {       // both scales finite and in [0, 1]
+    return std::isfinite(P.sx) && std::isfinite(P.sy) && P.sx >= 0.f && P.sy >= 0.f && P.sx <= 1.f && P.sy <= 1.f;
+}
+
+// separable patch edge: floor(span) + 1 tap offsets + 1 for the right/bottom tap + 1 for fp32 rounding, even
+int sep_patch_edge(const StackParams& P) {
+    const float span = 2.0f * P.radius * std::max(P.sx, P.sy);
+    return ((int)std::floor(span * (1.0f + 1e-5f) + 1e-4f) + 3 + 1) & ~1;
+}
+
+enum class StackFamily { Patch, Separable, General };
+struct StackRoute {
+    StackFamily family;
+    int R, K;                                     // Patch: R; Separable: R, K
+};
+
+StackRoute stack_route(const StackParams& P) {
+    const bool fits32 = stack_image_bytes(P) < kImageBytesMax;
+    if (P.sx == 1.0f && P.sy == 1.0f && P.radius >= 1 && P.radius <= 4 && fits32)
+        return {StackFamily::Patch, P.radius, 0};
+    if ((P.radius == 3 || P.radius == 4) && scale_in_01(P) && fits32) {
+        const int k = sep_patch_edge(P);
+        if (k == 4 || k == 6 || k == 8) return {StackFamily::Separable, P.radius, k};
+    }
+    return {StackFamily::General, 0, 0};
+}
+
+enum class StackBwdFamily { Patch2, Patch1, Separable2, Separable1, General, Fallback };
+struct StackBwdRoute {
+    StackBwdFamily family;
+    int R, K;                                     // Patch*: R; Separable*: K
+    bool small;                                   // LDS window: kWinSmall (16 KiB) or kWinFloats (48 KiB)
+};
+
+// LDS window: a workgroup's 256 pixels (512 with two pixels per lane) cover ~256/w + 1 rows; with the
+// patch (<= 2r+2 rows at unit steps) and some flow spread, 4096 floats (16 KiB) hold them for w up to
+// ~170 and leave room for 9 workgroups per CU instead of 3 (48 KiB); rows past the window still go to
+// global atomics, so the choice only affects speed.
+bool stack_small_window(const StackParams& P, int pixels) {
+    const float rows = 2.0f * P.radius * std::max(P.sy, 1.0f) + (float)pixels / P.w * std::max(P.sy, 0.5f) + 10.0f;
+    return rows * P.wl <= (float)kWinSmall;
+}
+
+StackBwdRoute stack_backward_route(const StackParams& P) {
+    if (P.sx == 1.0f && P.sy == 1.0f && P.radius >= 1 && P.radius <= 4) {
+        // two pixels per lane: the general two-pixel merge over the joint patch box + the cross-lane chain
+        // (0.55 vs 0.75 ms smooth flow, 0.77 vs 0.96 ms steep flow at cfg4 against the round-1 per-pixel
+        // adds, profiles/dicl_bwd_ab_r02.json); one pixel per lane for images past 4 GiB of stack
+        if (stack_image_bytes(P) < kImageBytesMax)
+            return {StackBwdFamily::Patch2, P.radius, 0, stack_small_window(P, 512)};
+        return {StackBwdFamily::Patch1, P.radius, 0, stack_small_window(P, 256)};
+    }
+    if (P.wl <= kWinFloats && scale_in_01(P)) {
+        // two pixels per lane with the merged / chained patch adds (K <= 8: 0.50 vs 0.68 ms smooth, 0.52 vs
+        // 0.61 ms steep flow at cfg4 level 1 against one pixel per lane); K = 10 one pixel per lane
+        const int k = sep_patch_edge(P);
+        if (k <= 8) return {StackBwdFamily::Separable2, 0, k, stack_small_window(P, 512)};   // k = 4, 6, 8
+        if (k == 10) return {StackBwdFamily::Separable1, 0, k, stack_small_window(P, 256)};
+    }
+    if (P.wl <= kWinFloats && std::isfinite(P.sx) && std::isfinite(P.sy) && P.sy >= 0.f)
+        return {StackBwdFamily::General, 0, 0, stack_small_window(P, 256)};
+    return {StackBwdFamily::Fallback, 0, 0, false};
+}
+
+std::string route_name(const StackRoute& r) {
+    switch (r.family) {
+        case StackFamily::Patch: return "patch/" + std::to_string(r.R);
+        case StackFamily::Separable: return "separable/" + std::to_string(r.R) + "/" + std::to_string(r.K);
+        default: return "general";
+    }
+}
+
+std::string route_name(const StackBwdRoute& r) {
+    const char* win = r.small ? "/small" : "/large";
+    switch (r.family) {
+        case StackBwdFamily::Patch2: return "patch2/" + std::to_string(r.R) + win;
+        case StackBwdFamily::Patch1: return "patch1/" + std::to_string(r.R) + win;
+        case StackBwdFamily::Separable2: return "separable2/" + std::to_string(r.K) + win;
+        case StackBwdFamily::Separable1: return "separable1/" + std::to_string(r.K) + win;
+        case StackBwdFamily::General: return std::string("general") + win;
+        default: return "fallback";
+    }
+}
+
+// every route the two functions above can return, in dispatch order; the strings live for the
+// life of the library, so the queries hand out pointers into them
+struct RouteNames {
+    std::vector<std::string> names;
+    std::string joined;
+    void add(const std::string& s) {
+        names.push_back(s);
+        joined += (joined.empty() ? "" : ",") + s;
+    }
+    const char* find(const std::string& s) const {
+        for (const std::string& n : names)
+            if (n == s) return n.c_str();
+        return nullptr;
+    }
+};
+
+const RouteNames& route_names(bool backward) {
+    static const RouteNames fwd = [] {
+        RouteNames t;
+        for (int r = 1; r <= 4; ++r) t.add(route_name(StackRoute{StackFamily::Patch, r, 0}));
+        for (int r = 3; r <= 4; ++r)
+            for (int k = 4; k <= 8; k += 2) t.add(route_name(StackRoute{StackFamily::Separable, r, k}));
+        t.add(route_name(StackRoute{StackFamily::General, 0, 0}));
+        return t;
+    }();
+    static const RouteNames bwd = [] {
+        RouteNames t;
+        for (StackBwdFamily f : {StackBwdFamily::Patch2, StackBwdFamily::Patch1})
+            for (int r = 1; r <= 4; ++r)
+                for (bool small : {true, false}) t.add(route_name(StackBwdRoute{f, r, 0, small}));
+        for (int k = 4; k <= 8; k += 2)
+            for (bool small : {true, false}) t.add(route_name(StackBwdRoute{StackBwdFamily::Separable2, 0, k, small}));
+        for (bool small : {true, false}) t.add(route_name(StackBwdRoute{StackBwdFamily::Separable1, 0, 10, small}));
+        for (bool small : {true, false}) t.add(route_name(StackBwdRoute{StackBwdFamily::General, 0, 0, small}));
+        t.add(route_name(StackBwdRoute{StackBwdFamily::Fallback, 0, 0, false}));
+        return t;
+    }();
+    return backward ? bwd : fwd;
+}
+
 // ---- backward warping (common/warp.py:5-33), alone or fused into the occlusion pass of the integer
 // volume (impls/dicl.py:178-181 -> 212-238) ---------------------------------------------------------
 // warped[c, p] = mask(p) * bilinear(img2[c], x + fx, y + fy) with zero padding, where mask(p) = the
@@ -1491,6 +1652,20 @@ warp_backward_kernel(const float* __restrict__ grad, const float* __restrict__ f
 
 using namespace rmd;
 
+extern "C" const char* rmd_dicl_stack_kernel(int batch, int channels, int height, int width, int level_height,
+                                             int level_width, int radius, int level, int norm_height,
+                                             int norm_width, int extra_delta, int backward) {
+    StackParams P;
+    if (stack_params(P, batch, channels, height, width, level_height, level_width, radius, level, norm_height,
+                     norm_width, extra_delta))
+        return "invalid";
+    const RouteNames& t = route_names(backward != 0);
+    const char* name = t.find(backward ? route_name(stack_backward_route(P)) : route_name(stack_route(P)));
+    return name ? name : "invalid";
+}
+
+extern "C" const char* rmd_dicl_stack_kernel_list(int backward) { return route_names(backward != 0).joined.c_str(); }
+
 extern "C" int rmd_dicl_stack(const float* fmap1, const float* fmap2, const float* coords, int batch, int channels,
                               int height, int width, int level_height, int level_width, int radius, int level,
                               int norm_height, int norm_width, int extra_delta, float* out, void* stream) {
@@ -1500,43 +1675,40 @@ extern "C" int rmd_dicl_stack(const float* fmap1, const float* fmap2, const floa
                           norm_width, extra_delta);
     if (rc) return rc;
     const int d = 2 * radius + 1;
-    const double image_bytes = 4.0 * d * d * (2.0 * channels + P.extra) * height * width;
-    if (P.sx == 1.0f && P.sy == 1.0f && radius >= 1 && radius <= 4 && image_bytes < 4294967296.0) {
-        // Measured at cfg4 (profiles/dicl_ab_r01.json, dicl_px_ab_r02.json): non-temporal stores are the
-        // win (0.33 -> 0.26 ms); one pixel per lane (56 VGPRs, 7 waves per SIMD instead of 4 with 2 or 4
-        // pixels per lane) keeps more stores in flight: 0.238 vs 0.256 ms; an XCD remap changes nothing
-        constexpr int px = 1;
-        const int nxb = (height * width / px + kThreads - 1) / kThreads;
-        const long long nwg = (long long)nxb * channels * batch;
-        RMD_REQUIRE(nwg < (1ll << 31), RMD_ERR_SHAPE, "rmd_dicl_stack: grid too large");
-        constexpr int remap = 0;
-        hipStream_t st = as_stream(stream);
-        switch (radius) {
+    hipStream_t st = as_stream(stream);
+    const StackRoute route = stack_route(P);
+    switch (route.family) {
+        case StackFamily::Patch: {
+            // Measured at cfg4 (profiles/dicl_ab_r01.json, dicl_px_ab_r02.json): non-temporal stores are the
+            // win (0.33 -> 0.26 ms); one pixel per lane (56 VGPRs, 7 waves per SIMD instead of 4 with 2 or 4
+            // pixels per lane) keeps more stores in flight: 0.238 vs 0.256 ms; an XCD remap changes nothing
+            constexpr int px = 1;
+            const int nxb = (height * width / px + kThreads - 1) / kThreads;
+            const long long nwg = (long long)nxb * channels * batch;
+            RMD_REQUIRE(nwg < (1ll << 31), RMD_ERR_SHAPE, "rmd_dicl_stack: grid too large");
+            constexpr int remap = 0;
+            switch (route.R) {
 #define RMD_CASE(RR) case RR: \
-            dicl_stack_patch_kernel<RR, px, true><<<(unsigned)nwg, kThreads, 0, st>>>(fmap1, fmap2, coords, P, nxb, remap, out); \
-            break;
-            RMD_CASE(1) RMD_CASE(2) RMD_CASE(3) RMD_CASE(4)
+                dicl_stack_patch_kernel<RR, px, true><<<(unsigned)nwg, kThreads, 0, st>>>(fmap1, fmap2, coords, P, nxb, remap, out); \
+                break;
+                RMD_CASE(1) RMD_CASE(2) RMD_CASE(3) RMD_CASE(4)
 #undef RMD_CASE
+            }
+            return check_launch("rmd_dicl_stack/patch");
         }
-        return check_launch("rmd_dicl_stack/patch");
+        case StackFamily::Separable: {
+            dim3 g1((height * width + kThreads - 1) / kThreads, channels, batch);
+            switch (route.R * 100 + route.K) {
+#define RMD_SCASE(RR, KK) case RR * 100 + KK: dicl_stack_sep_kernel<RR, KK, true><<<g1, kThreads, 0, st>>>(fmap1, fmap2, coords, P, out); break;
+                RMD_SCASE(3, 4) RMD_SCASE(3, 6) RMD_SCASE(3, 8) RMD_SCASE(4, 4) RMD_SCASE(4, 6) RMD_SCASE(4, 8)
+#undef RMD_SCASE
+            }
+            return check_launch("rmd_dicl_stack/separable");
+        }
+        case StackFamily::General: break;
     }
     dim3 grid((height * width / 4 + kThreads - 1) / kThreads, d * d, batch);
-    if ((radius == 3 || radius == 4) && std::isfinite(P.sx) && std::isfinite(P.sy) && P.sx >= 0.f &&
-        P.sy >= 0.f && P.sx <= 1.f && P.sy <= 1.f && image_bytes < 4294967296.0) {
-        const float span = 2.0f * radius * std::max(P.sx, P.sy);
-        const int k = ((int)std::floor(span * (1.0f + 1e-5f) + 1e-4f) + 3 + 1) & ~1;
-        dim3 g1((height * width + kThreads - 1) / kThreads, channels, batch);
-        hipStream_t st = as_stream(stream);
-        bool launched = true;
-        switch (radius * 100 + k) {
-#define RMD_SCASE(RR, KK) case RR * 100 + KK: dicl_stack_sep_kernel<RR, KK, true><<<g1, kThreads, 0, st>>>(fmap1, fmap2, coords, P, out); break;
-            RMD_SCASE(3, 4) RMD_SCASE(3, 6) RMD_SCASE(3, 8) RMD_SCASE(4, 4) RMD_SCASE(4, 6) RMD_SCASE(4, 8)
-#undef RMD_SCASE
-            default: launched = false;
-        }
-        if (launched) return check_launch("rmd_dicl_stack/separable");
-    }
-    dicl_stack_kernel<true, 1><<<grid, kThreads, 0, as_stream(stream)>>>(fmap1, fmap2, coords, P, out);
+    dicl_stack_kernel<true, 1><<<grid, kThreads, 0, st>>>(fmap1, fmap2, coords, P, out);
     return check_launch("rmd_dicl_stack");
 }
 
@@ -1551,82 +1723,50 @@ extern "C" int rmd_dicl_stack_backward(const float* grad_stack, const float* coo
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
     const int d = 2 * radius + 1;
-    // LDS window: a workgroup's 256 pixels cover ~256/w + 1 rows; with the patch (<= 2r+2 rows at
-    // unit steps) and some flow spread, 4096 floats (16 KiB) hold them for w up to ~170 and leave
-    // room for 9 workgroups per CU instead of 3 (48 KiB); rows past the window still go to global
-    // atomics, so the choice only affects speed.
-    const float rows_est = 2.0f * radius * std::max(P.sy, 1.0f) + 256.0f / width * std::max(P.sy, 0.5f) + 10.0f;
-    const bool small_win = rows_est * level_width <= (float)kWinSmall;
-    const double image_bytes = 4.0 * d * d * (2.0 * channels + P.extra) * height * width;
-    if (P.sx == 1.0f && P.sy == 1.0f && radius >= 1 && radius <= 4) {
-        (void)hipMemsetAsync(grad_fmap2, 0, sizeof(float) * (size_t)batch * channels * level_height * level_width, st);
-        dim3 grid((height * width + kThreads - 1) / kThreads, channels, batch);
-        // two pixels per lane: the general two-pixel merge over the joint patch box + the cross-lane chain
-        // (0.55 vs 0.75 ms smooth flow, 0.77 vs 0.96 ms steep flow at cfg4 against the round-1 per-pixel
-        // adds, profiles/dicl_bwd_ab_r02.json); one pixel per lane for images past 4 GiB of stack
-        if (image_bytes < 4294967296.0) {
-            const float rows2 = 2.0f * radius + 512.0f / width + 10.0f;
-            const bool small2 = rows2 * level_width <= (float)kWinSmall;
-            dim3 grid2((height * width / 2 + kThreads - 1) / kThreads, channels, batch);
-            switch (radius) {
-#define RMD_CASE(RR) case RR: \
-                if (small2) dicl_stack_patch_backward_gm_kernel<RR, kWinSmall, true><<<grid2, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-                else dicl_stack_patch_backward_gm_kernel<RR, kWinFloats, true><<<grid2, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-                break;
+    const StackBwdRoute route = stack_backward_route(P);
+    (void)hipMemsetAsync(grad_fmap2, 0, sizeof(float) * (size_t)batch * channels * level_height * level_width, st);
+    const dim3 grid((height * width + kThreads - 1) / kThreads, channels, batch);            // one pixel per lane
+    const dim3 grid2((height * width / 2 + kThreads - 1) / kThreads, channels, batch);       // two
+// the kernel (template arguments included) on GRID; RMD_WIN picks the route's LDS window
+#define RMD_RUN(GRID, ...) __VA_ARGS__<<<GRID, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2)
+#define RMD_WIN(GRID, KERNEL, ARG) \
+    if (route.small) RMD_RUN(GRID, KERNEL<ARG, kWinSmall>); \
+    else RMD_RUN(GRID, KERNEL<ARG, kWinFloats>)
+    switch (route.family) {
+        case StackBwdFamily::Patch2:
+            switch (route.R) {
+#define RMD_CASE(RR) case RR: if (route.small) RMD_RUN(grid2, dicl_stack_patch_backward_gm_kernel<RR, kWinSmall, true>); \
+                              else RMD_RUN(grid2, dicl_stack_patch_backward_gm_kernel<RR, kWinFloats, true>); \
+                              break;
                 RMD_CASE(1) RMD_CASE(2) RMD_CASE(3) RMD_CASE(4)
 #undef RMD_CASE
             }
             return check_launch("rmd_dicl_stack_backward/patch2");
-        }
-        switch (radius) {
-#define RMD_CASE(RR) case RR: \
-            if (small_win) dicl_stack_patch_backward_kernel<RR, kWinSmall><<<grid, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-            else dicl_stack_patch_backward_kernel<RR, kWinFloats><<<grid, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-            break;
-            RMD_CASE(1) RMD_CASE(2) RMD_CASE(3) RMD_CASE(4)
+        case StackBwdFamily::Patch1:
+            switch (route.R) {
+#define RMD_CASE(RR) case RR: RMD_WIN(grid, dicl_stack_patch_backward_kernel, RR); break;
+                RMD_CASE(1) RMD_CASE(2) RMD_CASE(3) RMD_CASE(4)
 #undef RMD_CASE
-        }
-        return check_launch("rmd_dicl_stack_backward/patch");
-    }
-    (void)hipMemsetAsync(grad_fmap2, 0, sizeof(float) * (size_t)batch * channels * level_height * level_width, st);
-    if (level_width <= kWinFloats && std::isfinite(P.sx) && std::isfinite(P.sy) && P.sy >= 0.f && P.sx >= 0.f &&
-        P.sx <= 1.f && P.sy <= 1.f) {
-        // patch edge: floor(span) + 1 tap offsets + 1 for the right/bottom tap + 1 for fp32 rounding, even
-        const float span = 2.0f * radius * std::max(P.sx, P.sy);
-        const int k = ((int)std::floor(span * (1.0f + 1e-5f) + 1e-4f) + 3 + 1) & ~1;
-        dim3 grid((height * width + kThreads - 1) / kThreads, channels, batch);
-        // two pixels per lane with the merged / chained patch adds (K <= 8: 0.50 vs 0.68 ms smooth, 0.52 vs
-        // 0.61 ms steep flow at cfg4 level 1 against one pixel per lane); K > 8 one pixel per lane
-        if (k <= 8) {
-            const float rows2 = 2.0f * radius * std::max(P.sy, 1.0f) + 512.0f / width * std::max(P.sy, 0.5f) + 10.0f;
-            const bool small2 = rows2 * level_width <= (float)kWinSmall;
-            dim3 grid2((height * width / 2 + kThreads - 1) / kThreads, channels, batch);
-            switch (k) {
-#define RMD_KCASE2(KK) case KK: \
-                if (small2) dicl_stack_sep_backward2_kernel<KK, kWinSmall><<<grid2, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-                else dicl_stack_sep_backward2_kernel<KK, kWinFloats><<<grid2, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-                return check_launch("rmd_dicl_stack_backward/separable2");
-                RMD_KCASE2(4) RMD_KCASE2(6) RMD_KCASE2(8)
-#undef RMD_KCASE2
-                default: break;
             }
-        }
-        switch (k) {
-#define RMD_KCASE(KK) case KK: \
-            if (small_win) dicl_stack_sep_backward_kernel<KK, kWinSmall><<<grid, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
-            else dicl_stack_sep_backward_kernel<KK, kWinFloats><<<grid, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2); \
+            return check_launch("rmd_dicl_stack_backward/patch");
+        case StackBwdFamily::Separable2:
+            switch (route.K) {
+#define RMD_CASE(KK) case KK: RMD_WIN(grid2, dicl_stack_sep_backward2_kernel, KK); break;
+                RMD_CASE(4) RMD_CASE(6) RMD_CASE(8)
+#undef RMD_CASE
+            }
+            return check_launch("rmd_dicl_stack_backward/separable2");
+        case StackBwdFamily::Separable1:
+            RMD_WIN(grid, dicl_stack_sep_backward_kernel, 10);
             return check_launch("rmd_dicl_stack_backward/separable");
-            RMD_KCASE(4) RMD_KCASE(6) RMD_KCASE(8) RMD_KCASE(10)
-#undef RMD_KCASE
-            default: break;
-        }
+        case StackBwdFamily::General:
+            if (route.small) RMD_RUN(grid, dicl_stack_general_backward_kernel<kWinSmall>);
+            else RMD_RUN(grid, dicl_stack_general_backward_kernel<kWinFloats>);
+            return check_launch("rmd_dicl_stack_backward/general");
+        case StackBwdFamily::Fallback: break;
     }
-    if (level_width <= kWinFloats && std::isfinite(P.sx) && std::isfinite(P.sy) && P.sy >= 0.f) {
-        dim3 grid((height * width + kThreads - 1) / kThreads, channels, batch);
-        if (small_win) dicl_stack_general_backward_kernel<kWinSmall><<<grid, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2);
-        else dicl_stack_general_backward_kernel<kWinFloats><<<grid, kThreads, 0, st>>>(grad_stack, coords, P, grad_fmap1, grad_fmap2);
-        return check_launch("rmd_dicl_stack_backward/general");
-    }
+#undef RMD_WIN
+#undef RMD_RUN
     dim3 g1((height * width / 4 + kThreads - 1) / kThreads, channels, batch);
     dicl_stack_grad_f1_kernel<<<g1, kThreads, 0, st>>>(grad_stack, P, grad_fmap1);
     dim3 g2((height * width + kThreads - 1) / kThreads, d * d, batch);

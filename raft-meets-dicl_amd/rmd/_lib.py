@@ -91,6 +91,8 @@ _SIGS = {
     "rmd_corr_grad_gemm": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "rmd_dicl_stack": (_I, [_P, _P, _P] + [_I] * 11 + [_P, _P]),
     "rmd_dicl_stack_backward": (_I, [_P, _P] + [_I] * 11 + [_P, _P, _P]),
+    "rmd_dicl_stack_kernel": (ctypes.c_char_p, [_I] * 12),
+    "rmd_dicl_stack_kernel_list": (ctypes.c_char_p, [_I]),
     "rmd_dicl_stack_int_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I]),
     "rmd_dicl_stack_int": (_I, [_P, _P] + [_I] * 6 + [_P, _P, _P]),
     "rmd_dicl_stack_int_backward": (_I, [_P, _P] + [_I] * 6 + [_P, _P, _P, _P]),

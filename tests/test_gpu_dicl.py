@@ -14,6 +14,7 @@ import torch
 
 import oracle
 from conftest import load_golden, rel_max_err
+from dicl_route_cases import INT_EDGE_CASES, int_edge_inputs
 
 DAP_TOL = 1e-4
 from detinit import det_init
@@ -181,6 +182,25 @@ def test_dicl_stack_int_cfg3_level2_vs_oracle():
     f2[:, :, 10:20, 30:50] = 0
     mvol = rmd.ops.dicl_stack_int(_t(f1), _t(f2), 3, 3).cpu().numpy()
     assert np.array_equal(mvol, oracle.dicl_stack_int(f1, f2, 3, 3))
+
+
+@pytest.mark.parametrize("b,c,h,w,ru,rv", INT_EDGE_CASES)
+def test_dicl_stack_int_edges_vs_oracle(b, c, h, w, ru, rv):
+    """The integer volume's 4-pixel lanes and 8-channel unroll off their usual shapes: widths that are
+    no multiple of 4 (a quad crosses a row end: w = 10, 6, 7), channel tails (C = 5, 33, 12), ru != rv
+    and a zero radius.  Bit-exact forward, gradients within 1e-6 (sums of <= (2ru+1)(2rv+1) terms)."""
+    import rmd
+    rng, f1, f2 = int_edge_inputs(b, c, h, w)
+    t1, t2 = _t(f1, True), _t(f2, True)
+    mvol = rmd.ops.dicl_stack_int(t1, t2, ru, rv)
+    ref = oracle.dicl_stack_int(f1, f2, ru, rv)
+    assert tuple(mvol.shape) == ref.shape
+    assert np.array_equal(mvol.detach().cpu().numpy(), ref)
+    gm = rng.standard_normal(ref.shape).astype(np.float32)
+    g1, g2 = torch.autograd.grad(mvol, (t1, t2), _t(gm))
+    r1, r2 = oracle.dicl_stack_int_backward(f1.astype(np.float64), f2.astype(np.float64), ru, rv, gm.astype(np.float64))
+    assert rel_max_err(g1.cpu().numpy(), r1) < 1e-6
+    assert rel_max_err(g2.cpu().numpy(), r2) < 1e-6
 
 
 def test_dap_golden():

@@ -14,6 +14,7 @@ import torch
 
 import oracle
 from conftest import load_golden, rel_max_err
+from dicl_route_cases import INT_EDGE_CASES, int_edge_inputs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -103,5 +104,21 @@ def test_warped_volume_cfg3_shape_vs_oracle():
     got = rmd.ops.dicl_stack_int_warped(_t(f1), _t(f2), _t(flow), 3, 3).cpu().numpy()
     warped, _ = oracle.warp_backwards(f2.astype(np.float64), flow.astype(np.float64))
     ref = oracle.dicl_stack_int(f1.astype(np.float64), warped, 3, 3)
+    assert np.array_equal(got == 0, ref == 0)
+    assert rel_max_err(got, ref) < 1e-5
+
+
+@pytest.mark.parametrize("b,c,h,w,ru,rv", INT_EDGE_CASES)
+def test_warped_volume_edges_vs_oracle(b, c, h, w, ru, rv):
+    """The warped integer volume at the edge shapes of test_dicl_stack_int_edges_vs_oracle (quads that
+    cross a row end, channel tails, ru != rv, a zero radius) under a sigma = 1 flow, with a zeroed f2
+    strip: the oracle's warp followed by its integer volume; zero pattern exact, values within 1e-5."""
+    import rmd
+    rng, f1, f2 = int_edge_inputs(b, c, h, w)
+    flow = rng.standard_normal((b, 2, h, w)).astype(np.float32)
+    got = rmd.ops.dicl_stack_int_warped(_t(f1), _t(f2), _t(flow), ru, rv).cpu().numpy()
+    warped, _ = oracle.warp_backwards(f2.astype(np.float64), flow.astype(np.float64))
+    ref = oracle.dicl_stack_int(f1.astype(np.float64), warped, ru, rv)
+    assert got.shape == ref.shape
     assert np.array_equal(got == 0, ref == 0)
     assert rel_max_err(got, ref) < 1e-5
