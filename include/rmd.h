@@ -424,6 +424,37 @@ int rmd_softargmax_backward(const float* cost, const float* grad_flows, int batc
                             int levels, int radius, float temperature, float* grad_cost, void* stream);
 
 /*
+ * DICL flow head: the two modules between the DAP and the context network of a DICL level, from one
+ * read of the cost.  Replaces FlowRegression.forward (src/models/impls/dicl.py:53-85),
+ * FlowEntropy.forward (dicl.py:31-50) and the coarse-flow addition of FlowLevel.compute_flow
+ * (dicl.py:195).  cost (B, du, dv, pixels) float32, du = 2 ru + 1 (dim 1: the u / x offset), dv = 2 rv + 1
+ * (dim 2: the v / y offset), ru and rv independent in 0..8; with D = du * dv:
+ *   p_ij      = softmax over all (i, j) of cost[b, i, j, :], max-subtracted
+ *   out[b, 0] = sum p_ij (i - ru)  (+ flow_coarse[b, 0]),   out[b, 1] = sum p_ij (j - rv)  (+ flow_coarse[b, 1])
+ *   out[b, 2] = -sum p_ij log(clamp(p_ij, eps, 1 - eps)) / log(D)
+ * all in float32 (1 - eps and log(D) included: 1 - 1e-9 is 1).  out (B, 3, pixels); flow_coarse
+ * (B, 2, pixels) or NULL; eps in [0, 0.5).  D = 1 gives flow 0 and entropy 0/0 = NaN, as the reference.
+ * A NaN or +inf cost at a pixel, or all costs -inf, makes its three outputs NaN (torch's softmax); a
+ * single -inf cost has p = 0 and adds 0 to the entropy.  Square windows of radius 1..4 keep the costs
+ * in registers; every other (ru, rv) reads them again per pass.
+ */
+int rmd_dicl_flow_head(const float* cost, const float* flow_coarse, int batch, int du, int dv, int pixels, float eps,
+                       float* out, void* stream);
+
+/*
+ * d cost (B, du, dv, pixels) of rmd_dicl_flow_head from grad_out (B, 3, pixels): autograd of dicl.py:43-50
+ * and :78-83 in one pass that recomputes p (nothing is saved by the forward):
+ *   grad_cost_k = p_k (g_k - sum_j p_j g_j),
+ *   g_k = gu u_k + gv v_k - gH (log(clamp(p_k, eps, 1 - eps)) + [eps <= p_k <= 1 - eps]) / log(D)
+ * (the bracket is torch's clamp subgradient), with g taken relative to the arg-max displacement so a
+ * peaked softmax keeps its relative accuracy.  No atomics, no workspace: bitwise reproducible.  A pixel
+ * whose outputs are NaN gets a NaN gradient, a -inf cost gradient 0.  The gradient with respect to
+ * flow_coarse is grad_out[:, :2] and needs no kernel.
+ */
+int rmd_dicl_flow_head_backward(const float* cost, const float* grad_out, int batch, int du, int dv, int pixels,
+                                float eps, float* grad_cost, void* stream);
+
+/*
  * Input format (src/models/input.py).  rmd_input_images replaces Input.__getitem__'s clip and range
  * map (input.py:215-221), ModuloPadding.apply (input.py:79-138) and TorchAdapter's permute to NCHW
  * (input.py:280-281) for one image tensor of a pair:

@@ -11,6 +11,9 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
   rmd.raft_dicl_ml.CorrelationModule    <- src/models/impls/raft_dicl_ml.py:235-343
   rmd.blocks.dicl                       <- src/models/common/blocks/dicl.py:93-150
   rmd.dicl.compute_cost                 <- src/models/impls/dicl.py:171-241 (+ fused warp)
+  rmd.dicl.FlowRegression / FlowEntropy / FlowLevelMixin
+                                        <- src/models/impls/dicl.py:31-85, 186-210 (one fused head pass,
+                                           rmd.ops.dicl_flow_head)
   rmd.warp.warp_backwards               <- src/models/common/warp.py:5-33
   rmd.raft.Up8Network / SoftArgMax*     <- src/models/impls/raft.py:98-190,299-331 (rmd.heads)
   rmd.input.InputSpec / ModuloPadding   <- src/models/input.py:32-313 (frame pair + flow target format)

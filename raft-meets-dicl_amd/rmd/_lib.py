@@ -112,6 +112,8 @@ _SIGS = {
     "rmd_up8_backward": (_I, [_P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P]),
     "rmd_softargmax": (_I, [_P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_softargmax_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
+    "rmd_dicl_flow_head": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
+    "rmd_dicl_flow_head_backward": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_sequence_loss_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
     "rmd_sequence_loss": (_I, [_P, _I, _P, _P] + [_I] * 6 + [ctypes.c_float, _P, _P, _P, _P]),
     "rmd_sequence_loss_backward": (_I, [_P, _I, _P, _P] + [_I] * 5 + [ctypes.c_float, _P, _P, _P]),

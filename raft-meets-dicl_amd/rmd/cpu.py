@@ -17,12 +17,14 @@ CPU-side formats:
     (the HIP workspace is an opaque byte buffer in the kernel's operand order).
 """
 
+import math
+
 import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _LOSS_SCHEMAS, _METRIC_SCHEMAS, _SCHEMAS, _STORAGE, check_loss_args, check_metric_args,
-                      pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
+from .library import (LIB, _HEAD_SCHEMAS, _LOSS_SCHEMAS, _METRIC_SCHEMAS, _SCHEMAS, _STORAGE, check_head_args,
+                      check_loss_args, check_metric_args, pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
 def _delta(r, device):
@@ -469,6 +471,54 @@ assert sorted(_METRIC_KERNELS) == sorted(_METRIC_SCHEMAS), "every rmd metric ope
 for _name, _fn in _METRIC_KERNELS.items():
     LIB.impl(_name, _fn, "CPU")         # not differentiable: library.py's Autograd kernel serves every device
 
+# ---- DICL flow head (impls/dicl.py:31-85, 194-195, 202) --------------------------------------------
+
+def flow_regression(cost):
+    """FlowRegression.forward, dicl.py:59-85 -> (B, 2, h, w)."""
+    batch, du, dv, h, w = cost.shape
+    ru, rv = (du - 1) // 2, (dv - 1) // 2
+    disp_u = torch.arange(-ru, ru + 1, device=cost.device, dtype=torch.float32)     # dicl.py:64-66
+    disp_u = disp_u.view(du, 1).expand(-1, dv)
+    disp_v = torch.arange(-rv, rv + 1, device=cost.device, dtype=torch.float32)     # dicl.py:69-71
+    disp_v = disp_v.view(1, dv).expand(du, -1)
+    disp = torch.stack((disp_u, disp_v), dim=0).view(1, 2, du, dv, 1, 1)            # dicl.py:74-75
+    prob = F.softmax(cost.reshape(batch, du * dv, h, w), dim=1)                     # dicl.py:78-79
+    prob = prob.view(batch, 1, du, dv, h, w)
+    return (prob * disp).sum(dim=(2, 3))                                            # dicl.py:83
+
+
+def flow_entropy(cost, eps=1e-9):
+    """FlowEntropy.forward, dicl.py:39-50 -> (B, h, w)."""
+    batch, du, dv, h, w = cost.shape
+    x = F.softmax(cost.reshape(batch, du * dv, h, w), dim=1).view(batch, du, dv, h, w)     # dicl.py:43-45
+    entropy = (-x * torch.clamp(x, eps, 1.0 - eps).log()).sum(dim=(1, 2))           # dicl.py:48
+    return entropy / math.log(du * dv)                                              # dicl.py:50
+
+
+def dicl_flow_head_eager(cost, flow_coarse, eps):
+    """The reference's two modules and its coarse-flow addition, one after the other (dicl.py:194-195,
+    202) -> (flow, entropy (B, 1, h, w))."""
+    batch, _, _, h, w = cost.shape
+    flow = flow_regression(cost)
+    flow = flow + flow_coarse if flow_coarse is not None else flow
+    return flow, flow_entropy(cost, eps).view(batch, 1, h, w)
+
+
+def dicl_flow_head(cost, flow_coarse, eps):
+    check_head_args(cost, flow_coarse, eps)
+    return torch.cat(dicl_flow_head_eager(cost.float(), None if flow_coarse is None else flow_coarse.float(), eps), 1)
+
+
+def dicl_flow_head_backward(grad, cost, eps):
+    check_head_args(cost, None, eps, grad)
+    with torch.enable_grad():
+        c = cost.detach().float().requires_grad_(True)
+        return torch.autograd.grad(dicl_flow_head(c, None, eps), c, grad.float())[0]
+
+
+_HEAD_KERNELS = {"dicl_flow_head": dicl_flow_head, "dicl_flow_head_backward": dicl_flow_head_backward}
+assert sorted(_HEAD_KERNELS) == sorted(_HEAD_SCHEMAS), "every rmd head operator needs a CPU kernel"
+
 _KERNELS = {
     "corr_pyramid": corr_pyramid, "corr_lookup": corr_lookup,
     "corr_otf_prepare": corr_otf_prepare, "corr_otf_lookup": corr_otf_lookup,
@@ -481,6 +531,6 @@ _KERNELS = {
 }
 assert sorted(_KERNELS) == sorted(_SCHEMAS), "every rmd operator needs a CPU kernel"
 
-for _name, _fn in list(_KERNELS.items()) + list(_LOSS_KERNELS.items()):
+for _name, _fn in list(_KERNELS.items()) + list(_LOSS_KERNELS.items()) + list(_HEAD_KERNELS.items()):
     LIB.impl(_name, _fn, "CPU")
     LIB.impl(_name, _fn, "AutogradCPU")

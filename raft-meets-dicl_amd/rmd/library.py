@@ -18,6 +18,8 @@ is again an rmd operator.  Schemas follow SURVEY.md §8(b):
   warp_backwards(img2, flow, eps) -> (est, mask)                             common/warp.py:5-33
   sequence_loss(flows[], target, valid, masks[], ...) -> (loss, counts)      raft.py:616-644, loss/mlseq.py:34-67,
         (the loss operators, listed by loss_operators())                     raft_dicl_ctf_l3.py:430-473, dicl.py:436-472
+  dicl_flow_head(cost, flow_coarse?, eps) -> (B, 3, h, w) flow + entropy     impls/dicl.py:31-85, 194-195, 202
+        (the head operators, listed by head_operators())
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -929,6 +931,108 @@ def _flow_metrics_below_autograd(estimates, target, valid, distances, fl_abs, fl
 LIB.impl("flow_metrics", _flow_metrics_below_autograd, "Autograd")
 
 
+# ---- DICL flow head ------------------------------------------------------------------------------
+#
+# A fourth table: head_operators().  One operator serves FlowRegression, FlowEntropy and the coarse-flow
+# addition of a DICL level (impls/dicl.py:31-85, :195): out (B, 3, h, w) holds the flow in channels 0-1
+# and the normalised entropy in channel 2.  Its autograd formula recomputes the softmax from the cost
+# (dicl_flow_head_backward); the gradient of flow_coarse is the first two channels of the upstream one.
+
+_HEAD_SCHEMAS = {
+    "dicl_flow_head": "dicl_flow_head(Tensor cost, Tensor? flow_coarse, float eps) -> Tensor",
+    "dicl_flow_head_backward": "dicl_flow_head_backward(Tensor grad, Tensor cost, float eps) -> Tensor",
+}
+for _s in _HEAD_SCHEMAS.values():
+    LIB.define(_s)
+
+HEAD_MAX_RANGE = 8
+
+
+def check_head_args(cost, flow_coarse, eps, grad=None):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of the head operators."""
+    if cost.dim() != 5:
+        raise ValueError(f"dicl_flow_head: cost must be (B, du, dv, h, w), got {tuple(cost.shape)}")
+    b, du, dv, h, w = cost.shape
+    if du % 2 != 1 or dv % 2 != 1 or du > 2 * HEAD_MAX_RANGE + 1 or dv > 2 * HEAD_MAX_RANGE + 1:
+        raise ValueError(f"dicl_flow_head: du = {du}, dv = {dv} must be odd (2r + 1) with ranges 0..{HEAD_MAX_RANGE}")
+    if b < 1 or h < 1 or w < 1:
+        raise ValueError(f"dicl_flow_head: empty cost {tuple(cost.shape)}")
+    if not 0.0 <= eps < 0.5:
+        raise ValueError(f"dicl_flow_head: eps {eps} not in [0, 0.5)")
+    for name, t, ch in (("flow_coarse", flow_coarse, 2), ("grad", grad, 3)):
+        if t is None:
+            continue
+        if tuple(t.shape) != (b, ch, h, w):
+            raise ValueError(f"dicl_flow_head: {name} must be ({b}, {ch}, {h}, {w}), got {tuple(t.shape)}")
+    for name, t in (("cost", cost), ("flow_coarse", flow_coarse), ("grad", grad)):
+        if t is not None and not t.is_floating_point():
+            raise ValueError(f"dicl_flow_head: {name} must be a floating-point tensor, got {t.dtype}")
+
+
+def _dicl_flow_head(cost, flow_coarse, eps):
+    check_head_args(cost, flow_coarse, eps)
+    _all_gpu("dicl_flow_head", *([cost] if flow_coarse is None else [cost, flow_coarse]))
+    cc = _f32(cost)
+    fc = None if flow_coarse is None else _f32(flow_coarse)
+    b, du, dv, h, w = cc.shape
+    out = torch.empty((b, 3, h, w), dtype=torch.float32, device=cc.device)
+    with _Dev(cc) as st:
+        _lib.check(_lib.lib().rmd_dicl_flow_head(_ptr(cc), None if fc is None else _ptr(fc), b, du, dv, h * w,
+                                                 float(eps), _ptr(out), st), "rmd_dicl_flow_head")
+    return out
+
+
+LIB.impl("dicl_flow_head", _dicl_flow_head, "CUDA")
+
+
+@_fake("dicl_flow_head")
+def _(cost, flow_coarse, eps):
+    check_head_args(cost, flow_coarse, eps)
+    b, _, _, h, w = cost.shape
+    return cost.new_empty((b, 3, h, w), dtype=torch.float32)
+
+
+def _dicl_flow_head_backward(grad, cost, eps):
+    check_head_args(cost, None, eps, grad)
+    _all_gpu("dicl_flow_head_backward", grad, cost)
+    g, cc = _f32(grad), _f32(cost)
+    b, du, dv, h, w = cc.shape
+    gc = torch.empty_like(cc)
+    with _Dev(cc) as st:
+        _lib.check(_lib.lib().rmd_dicl_flow_head_backward(_ptr(cc), _ptr(g), b, du, dv, h * w, float(eps), _ptr(gc),
+                                                          st), "rmd_dicl_flow_head_backward")
+    return gc
+
+
+LIB.impl("dicl_flow_head_backward", _dicl_flow_head_backward, "CUDA")
+
+
+@_fake("dicl_flow_head_backward")
+def _(grad, cost, eps):
+    check_head_args(cost, None, eps, grad)
+    return cost.new_empty(cost.shape, dtype=torch.float32)
+
+
+def _head_setup(ctx, inputs, output):
+    cost, flow_coarse, eps = inputs
+    ctx.save_for_backward(cost)
+    ctx.eps = eps
+    ctx.coarse_dtype = None if flow_coarse is None else flow_coarse.dtype
+
+
+def _head_bwd(ctx, grad):
+    (cost,) = ctx.saved_tensors
+    gc = gf = None
+    if ctx.needs_input_grad[0]:
+        gc = torch.ops.rmd.dicl_flow_head_backward(grad, cost, ctx.eps).to(cost.dtype)
+    if ctx.coarse_dtype is not None and ctx.needs_input_grad[1]:
+        gf = grad[:, :2].to(ctx.coarse_dtype)
+    return gc, gf, None
+
+
+torch.library.register_autograd("rmd::dicl_flow_head", _head_bwd, setup_context=_head_setup)
+
+
 def operators():
     """Names of the registered torch.ops.rmd model operators."""
     return sorted(_SCHEMAS)
@@ -942,3 +1046,8 @@ def loss_operators():
 def metric_operators():
     """Names of the registered torch.ops.rmd metric operators."""
     return sorted(_METRIC_SCHEMAS)
+
+
+def head_operators():
+    """Names of the registered torch.ops.rmd DICL flow-head operators."""
+    return sorted(_HEAD_SCHEMAS)

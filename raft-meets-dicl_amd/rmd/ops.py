@@ -503,6 +503,18 @@ def softargmax(cost, levels, radius, temperature=1.0):
     return list(torch.ops.rmd.softargmax(cost, levels, radius, float(temperature)).unbind(0))
 
 
+def dicl_flow_head(cost, flow_coarse=None, eps=1e-9):
+    """cost (B, du, dv, h, w) [+ flow_coarse (B, 2, h, w)] -> (flow (B, 2, h, w), entropy (B, 1, h, w)): the
+    soft-argmin flow (plus the coarse flow) and the normalised entropy of the same softmax, two views of
+    the one (B, 3, h, w) output of torch.ops.rmd.dicl_flow_head (impls/dicl.py:31-85, 194-195, 202)."""
+    if flow_coarse is None:
+        _same_device(cost)
+    else:
+        _same_device(cost, flow_coarse)
+    out = torch.ops.rmd.dicl_flow_head(cost, flow_coarse, float(eps))
+    return out[:, :2], out[:, 2:]
+
+
 # ---- sequence losses -----------------------------------------------------------------------------
 
 LOSS_ORDS = {1: _lib.RMD_LOSS_L1, 2: _lib.RMD_LOSS_L2, "absmean": _lib.RMD_LOSS_ABSMEAN,
