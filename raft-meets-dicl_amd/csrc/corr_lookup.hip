@@ -28,6 +28,21 @@ namespace {
 constexpr int kThreads = 64;       // one wave per workgroup: 25.64 vs 25.89 us (256) in the bench
                                    // sequence (profiles/lookup_threads_r01.json)
 
+// A/B knob: the instruction-stream reductions of the BUF paths, one bit each (same loads, stores and
+// results in every combination; profiles/lookup_instr_r10.json):
+//   1  fp16 differences as v_fma_mix_f32 on the packed halves (no separate fp16 -> fp32 converts)
+//   2  barrel shift: the fp16 half-word step as one v_alignbit per word by a per-lane 0 / 16 bits
+//   8  (wave, level) invariants: 32-bit slab sizes, shifts for floor divisions, level / part without a
+//      division, running row and plane offsets instead of multiplies
+// (Bit 4 was the load offsets as one row select and one column mask per load instead of the `valid`
+// chains: 0.8 us slower cache-resident and 65-67 VGPRs; measured, dropped and removed.)
+#ifndef RMD_LOOKUP_DIET
+#define RMD_LOOKUP_DIET 11
+#endif
+constexpr bool kDietMix = (RMD_LOOKUP_DIET & 1) != 0, kDietBarrel = (RMD_LOOKUP_DIET & 2) != 0,
+               kDietHoist = (RMD_LOOKUP_DIET & 8) != 0;
+
+
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 template <int NB> struct Chunk;
@@ -65,9 +80,28 @@ template <> __device__ __forceinline__ float word_elem<__half>(unsigned w, int i
 
 __device__ __forceinline__ int floor_div(int a, int d) { return a >= 0 ? a / d : -((d - 1 - a) / d); }
 
+// v1 - v0.  MIX (fp16 words, RMD_LOOKUP_DIET & 1): fma(v1, one, -v0) with an opaque one = 1.0f, so the
+// fp16 -> fp32 converts of both values fold into a v_fma_mix_f32's operands; one rounding of the exact
+// difference either way, so the same bits.
+template <bool MIX>
+__device__ __forceinline__ float diff_f32(float v1, float v0, float one) {
+    if constexpr (MIX) return __builtin_fmaf(v1, one, -v0);
+    else return v1 - v0;
+}
+__device__ __forceinline__ float opaque_one() {
+    float one = 1.0f;
+    asm("" : "+s"(one));
+    return one;
+}
+
 // Shift NW words (+1 zero word) left by sh elements of T (sh < TW): whole words in log steps, then a
 // half-word for fp16, and extract the K patch values with zero padding outside [0, lw) / bad rows.
-template <typename T, int K, int TW, int NW, bool MASK = true>
+//
+// LEAN (the BUF paths, RMD_LOOKUP_DIET & 2): the half-word shift is one v_alignbit per word that holds
+// patch values, by a per-lane 0 or 16 bits — no select between the shifted and the unshifted word.
+// (The whole-word steps stay as they are: the compiler already drops the selects nothing reads, and
+// run from the largest step down it merges them into one compare per word and shift amount.)
+template <typename T, int K, int TW, int NW, bool MASK = true, bool LEAN = false>
 __device__ __forceinline__ void shift_extract(unsigned (&wd)[NW + 1], int sh, int xs, int lw, bool row_ok,
                                               float (&v)[K]) {
     constexpr int S = sizeof(T);
@@ -81,7 +115,11 @@ __device__ __forceinline__ void shift_extract(unsigned (&wd)[NW + 1], int sh, in
 #pragma unroll
         for (int i = 0; i < NW + 1; ++i) wd[i] = on ? ((i + step < NW + 1) ? wd[i + step] : 0u) : wd[i];
     }
-    if constexpr (S == 2) {
+    if constexpr (S == 2 && LEAN) {
+        const unsigned bits = ((unsigned)sh & 1u) << 4;
+#pragma unroll
+        for (int i = 0; i < KW - 1; ++i) wd[i] = __builtin_amdgcn_alignbit(wd[i + 1], wd[i], bits);
+    } else if constexpr (S == 2) {
         const bool odd = (sh & 1) != 0;
 #pragma unroll
         for (int i = 0; i < KW; ++i) wd[i] = odd ? __builtin_amdgcn_alignbyte(wd[i + 1], wd[i], 2) : wd[i];
@@ -125,7 +163,6 @@ __device__ unsigned g_abl_off = 0x80000000u;
 #define RMD_LOOKUP_LAUX 0
 #endif
 constexpr int kLoadAux = RMD_LOOKUP_LAUX;
-
 // RMD_S24 storage element (include/rmd.h): bytes 1..3 of an fp32 word, little endian
 struct s24_t {
     unsigned char b[3];
@@ -140,6 +177,17 @@ __device__ __forceinline__ const T* level_base(const T* pyr, const PyrGeom& g, i
 
 template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t level_rsrc(const T* pyr, const PyrGeom& g, int L, int b) {
+    if constexpr (kDietHoist) {
+        // the host checked per * sizeof(T) < 2^31 for every level: 32-bit products, one 32 x 32 -> 64 for b
+        const unsigned per = (unsigned)g.ty[L] * (unsigned)g.tx[L] * (unsigned)g.slots * (unsigned)(g.th[L] * g.tw[L]);
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(pyr) + g.off[L] * (long long)sizeof(T) +
+                                    (unsigned long long)(unsigned)b * (per * (unsigned)sizeof(T));
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base);
+        const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
+        return __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<void*>(reinterpret_cast<const void*>(((uintptr_t)hi << 32) | lo)), (short)0,
+            (int)__builtin_amdgcn_readfirstlane(per * (unsigned)sizeof(T)), 0x00020000);
+    }
     const long long per = (long long)g.ty[L] * g.tx[L] * g.slots * g.th[L] * g.tw[L];     // elements per image
     const T* base = level_base(pyr, g, L, b);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base);
@@ -252,6 +300,18 @@ __device__ __forceinline__ OutBuf out_buf(float* o_block, int N, int D, int p, b
 template <int D>
 __device__ __forceinline__ void emit_row_buf(const OutBuf& ob, int N, int bb, float fy, const float (&hprev)[D],
                                              const float (&hcur)[D]) {
+    if constexpr (kDietHoist) {
+        // plane (a, bb) at (a * D + bb) * N * 4 bytes: one multiply per row, then adds of the D-plane stride
+        const unsigned dn4 = __builtin_amdgcn_readfirstlane((unsigned)(D * 4) * (unsigned)N);
+        unsigned so = __builtin_amdgcn_readfirstlane((unsigned)bb * (unsigned)N * 4u);
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(fmaf(fy, hcur[a] - hprev[a], hprev[a])), ob.rs,
+                                                  (int)ob.voff, (int)so, 2);
+            so += dn4;
+        }
+        return;
+    }
 #pragma unroll
     for (int a = 0; a < D; ++a)
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(fmaf(fy, hcur[a] - hprev[a], hprev[a])), ob.rs, (int)ob.voff,
@@ -314,37 +374,45 @@ __device__ __forceinline__ void rows_body_buf(__amdgpu_buffer_rsrc_t rs, const P
     constexpr int CB = CW * (int)sizeof(T);                         // chunk bytes
     constexpr int CWW = S24 ? CW : CB / 4;                          // chunk words (S24: widened)
     constexpr int NC = (K + CW - 1 + CW - 1) / CW;                  // chunks a row can span
+    constexpr bool MIX = kDietMix && std::is_same<TE, __half>::value;
     const int lh = g.lh[L], lw = g.lw[L], txs = g.tx[L];
     const unsigned cs = (unsigned)g.slots * CB, rsb = (unsigned)txs * cs;
-    const int tc0 = floor_div(xs, CW);
-    const int sh = xs - tc0 * CW;
+    static_assert((CW & (CW - 1)) == 0, "chunk widths are powers of two");
+    const int tc0 = kDietHoist ? xs >> (CW == 8 ? 3 : (CW == 4 ? 2 : 1)) : floor_div(xs, CW);
+    const int sh = kDietHoist ? (xs & (CW - 1)) : xs - tc0 * CW;
     const unsigned off0 = (unsigned)tc0 * cs + (unsigned)slot * CB;  // wraps for tc0 < 0: used only when valid
+    // (the chunk stride c * cs cannot go in the loads' scalar offset: the range check sees the vector
+    // offset alone, which wraps below zero for a window that starts left of the level until c * cs is added)
+    unsigned roff_run = off0 + (unsigned)(ys + bb0) * rsb;
+    const float one = MIX ? opaque_one() : 1.0f;
     float hprev[D];
 #pragma unroll
     for (int jj = 0; jj < KR; ++jj) {
         const int j = bb0 + jj;
         const int yy = ys + j;
         const bool rv = yy >= 0 && yy < lh;
-        const unsigned roff = off0 + (unsigned)yy * rsb;
+        const unsigned roff = kDietHoist ? roff_run : off0 + (unsigned)yy * rsb;
+        roff_run += rsb;
         unsigned wd[NC * CWW + 1];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int tc = tc0 + c;
             const bool valid = rv && tc >= 0 && tc < txs && c * CW < sh + K;
+            const unsigned off = valid ? roff + (unsigned)c * cs : kOOB;
             unsigned tmp[CWW];
             if constexpr (S24)
-                buf_s24<CW>(tmp, rs, valid ? roff + (unsigned)c * cs : kOOB);
+                buf_s24<CW>(tmp, rs, off);
             else
-                buf_words<CWW>(tmp, rs, valid ? roff + (unsigned)c * cs : kOOB);
+                buf_words<CWW>(tmp, rs, off);
 #pragma unroll
             for (int i = 0; i < CWW; ++i) wd[c * CWW + i] = tmp[i];
         }
         wd[NC * CWW] = 0u;
         float v[K];
-        shift_extract<TE, K, CW, NC * CWW, MASK>(wd, sh, xs, lw, true, v);
+        shift_extract<TE, K, CW, NC * CWW, MASK, kDietBarrel>(wd, sh, xs, lw, true, v);
         float hcur[D];
 #pragma unroll
-        for (int a = 0; a < D; ++a) hcur[a] = fmaf(fx, v[a + 1] - v[a], v[a]);
+        for (int a = 0; a < D; ++a) hcur[a] = fmaf(fx, diff_f32<MIX>(v[a + 1], v[a], one), v[a]);
         if (jj > 0 && (PR == D || j - 1 >= own0)) emit_row_buf<D>(ob, N, j - 1, fy, hprev, hcur);
 #pragma unroll
         for (int a = 0; a < D; ++a) hprev[a] = hcur[a];
@@ -415,11 +483,12 @@ __device__ __forceinline__ void tiles_body(const __half* __restrict__ pyr, const
     constexpr int NCR = KR / 2 + 1;                                 // chunk rows a part can span
     constexpr int NQ = (K + 3 + 3) / 4;                             // quads a patch row can span
     const int lh = g.lh[L], lw = g.lw[L];
+    constexpr bool HOIST = BUF && kDietHoist;
     const int ya = ys + bb0;
-    const int cr0 = floor_div(ya, 2);
-    const int par = ya - 2 * cr0;
-    const int q0 = floor_div(xs, 4);
-    const int sh = xs - 4 * q0;                                     // 0 .. 3
+    const int cr0 = HOIST ? ya >> 1 : floor_div(ya, 2);
+    const int par = HOIST ? (ya & 1) : ya - 2 * cr0;
+    const int q0 = HOIST ? xs >> 2 : floor_div(xs, 4);
+    const int sh = HOIST ? (xs & 3) : xs - 4 * q0;                  // 0 .. 3
     const int tys = g.ty[L], txs = g.tx[L];
 
     // BUF: per patch row, NQ 8-B loads straight from the row's half of each chunk (no parity select;
@@ -469,6 +538,8 @@ __device__ __forceinline__ void tiles_body(const __half* __restrict__ pyr, const
         }
     }
 
+    constexpr bool MIX = BUF && kDietMix;
+    const float one = MIX ? opaque_one() : 1.0f;
     float hprev[D];
 #pragma unroll
     for (int jj = 0; jj < KR; ++jj) {
@@ -493,10 +564,10 @@ __device__ __forceinline__ void tiles_body(const __half* __restrict__ pyr, const
         }
         rw[2 * NQ] = 0u;
         float v[K];
-        shift_extract<__half, K, 4, 2 * NQ, MASK>(rw, sh, xs, lw, row_ok, v);
+        shift_extract<__half, K, 4, 2 * NQ, MASK, BUF && kDietBarrel>(rw, sh, xs, lw, row_ok, v);
         float hcur[D];
 #pragma unroll
-        for (int a = 0; a < D; ++a) hcur[a] = fmaf(fx, v[a + 1] - v[a], v[a]);
+        for (int a = 0; a < D; ++a) hcur[a] = fmaf(fx, diff_f32<MIX>(v[a + 1], v[a], one), v[a]);
         const int j = bb0 + jj;
         if (jj > 0 && (PR == D || j - 1 >= own0)) {
             if constexpr (BUF) emit_row_buf<D>(ob, N, j - 1, fy, hprev, hcur);
@@ -544,8 +615,16 @@ corr_lookup_kernel(const T* __restrict__ pyr, PyrGeom g, const float* __restrict
                    float* __restrict__ out) {
     const int N = g.height * g.width;
     const int s = blockIdx.x * kThreads + threadIdx.x;
-    const int L = (int)blockIdx.z % g.levels;
-    const int part = (int)blockIdx.z / g.levels;
+    int L, part;
+    if constexpr (BUF && kDietHoist) {
+        // gridDim.z = 3 * levels (launch_lookup): z / levels and z % levels without the division
+        const int z = (int)blockIdx.z;
+        part = (z >= g.levels ? 1 : 0) + (z >= 2 * g.levels ? 1 : 0);
+        L = z - part * g.levels;
+    } else {
+        L = (int)blockIdx.z % g.levels;
+        part = (int)blockIdx.z / g.levels;
+    }
     const int b = blockIdx.y;
     bool active;
     int p, slot;
