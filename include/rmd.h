@@ -455,6 +455,41 @@ int rmd_dicl_flow_head_backward(const float* cost, const float* grad_out, int ba
                                 float eps, float* grad_cost, void* stream);
 
 /*
+ * Local cross-attention of the hidden-state upsampler HUpCrossAttn (src/models/common/hsup.py:71-92):
+ * q (B, ck, h, w) float32 from the fine level, k (B, ck, h2, w2) and v (B, cv, h2, w2) from the coarse
+ * one, out (B, cv, h, w).  h = fy h2 and w = fx w2 with integer factors 1..64; wy, wx in {1, 3, 5}.  For
+ * the fine pixel (y, x) with parent cell (Y, X) = (y / fy, x / fx) and window entry j = (jy, jx):
+ *   cell_j = (Y + jy - wy/2, X + jx - wx/2)
+ *   s_j    = sum_c q[c, y, x] k[c, cell_j]      a cell outside the map is a zero key: logit 0, not masked
+ *   a      = softmax(s)                         the maximum subtracted, no 1/sqrt(ck) scaling
+ *   out[c, y, x] = sum_j a_j v[c, cell_j]       a cell outside the map is a zero value
+ * (F.unfold's zero padding, hsup.py:71, :76).  One launch; K and V are never expanded to the fine
+ * resolution.  A weight is always multiplied with its value, so non-finite inputs spread as in the
+ * reference (0 * inf = NaN; a NaN logit makes the pixel's softmax NaN).
+ * rmd_local_cross_attn_kernel names the route a call takes: "w3x3_f2x2" (the models' 3 x 3 window at
+ * factor 2 x 2), "generic", or "invalid" for arguments the calls refuse (host only).
+ */
+const char* rmd_local_cross_attn_kernel(int batch, int ck, int cv, int h, int w, int h2, int w2, int wy, int wx);
+int rmd_local_cross_attn(const float* q, const float* k, const float* v, int batch, int ck, int cv, int h, int w,
+                         int h2, int w2, int wy, int wx, float* out, void* stream);
+
+/*
+ * Gradients of rmd_local_cross_attn from grad_out (B, cv, h, w); only q, k and v are read again, the
+ * softmax is recomputed.  With g = grad_out at a pixel:
+ *   da_j = sum_c g[c] v[c, cell_j],  ds_j = a_j (da_j - sum_i a_i da_i)
+ *   grad_q[c] = sum_j ds_j k[c, cell_j]
+ *   grad_k[c, cell] = sum of ds_{p,j} q_p[c], grad_v[c, cell] = sum of a_{p,j} g_p[c]
+ * over every fine pixel p and entry j with cell_j(p) = cell.  A pass per fine pixel writes grad_q and
+ * a, ds to `workspace` (rmd_local_cross_attn_workspace_bytes() bytes: (B, 2 wy wx, h, w) float32); a
+ * pass per coarse cell then adds its wy wx neighbour cells x fy fx fine pixels in a fixed order.  No
+ * atomics: bitwise reproducible.  All three gradients are written.
+ */
+size_t rmd_local_cross_attn_workspace_bytes(int batch, int h, int w, int wy, int wx);
+int rmd_local_cross_attn_backward(const float* grad_out, const float* q, const float* k, const float* v, int batch,
+                                  int ck, int cv, int h, int w, int h2, int w2, int wy, int wx, float* grad_q,
+                                  float* grad_k, float* grad_v, void* workspace, void* stream);
+
+/*
  * Input format (src/models/input.py).  rmd_input_images replaces Input.__getitem__'s clip and range
  * map (input.py:215-221), ModuloPadding.apply (input.py:79-138) and TorchAdapter's permute to NCHW
  * (input.py:280-281) for one image tensor of a pair:

@@ -14,6 +14,9 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
   rmd.dicl.FlowRegression / FlowEntropy / FlowLevelMixin
                                         <- src/models/impls/dicl.py:31-85, 186-210 (one fused head pass,
                                            rmd.ops.dicl_flow_head)
+  rmd.hsup.HUpNone / HUpBilinear / HUpCrossAttn / make_hidden_state_upsampler
+                                        <- src/models/common/hsup.py:8-108 (one fused local cross-attention
+                                           pass, rmd.ops.local_cross_attn)
   rmd.warp.warp_backwards               <- src/models/common/warp.py:5-33
   rmd.raft.Up8Network / SoftArgMax*     <- src/models/impls/raft.py:98-190,299-331 (rmd.heads)
   rmd.input.InputSpec / ModuloPadding   <- src/models/input.py:32-313 (frame pair + flow target format)
@@ -25,7 +28,8 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
                                            (one fused statistics pass, rmd.ops.flow_metrics)
 """
 
-from . import blocks, config, corr, cpu, dicl, heads, input, loss, metrics, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
+from . import blocks, config, corr, cpu, dicl, heads, hsup, input, loss, metrics, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
+from .hsup import HUpBilinear, HUpCrossAttn, HUpNone, make_hidden_state_upsampler  # noqa: F401
 from .loss import MultiLevelSequenceLoss, MultiscaleLoss, RestrictedMultiLevelSequenceLoss, SequenceLoss  # noqa: F401
 from .metrics import FlowMetrics  # noqa: F401
 from .ops import set_default_precision, get_default_precision  # noqa: F401

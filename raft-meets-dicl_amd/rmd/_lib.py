@@ -114,6 +114,10 @@ _SIGS = {
     "rmd_softargmax_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_dicl_flow_head": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_dicl_flow_head_backward": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
+    "rmd_local_cross_attn_kernel": (ctypes.c_char_p, [_I] * 9),
+    "rmd_local_cross_attn": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P]),
+    "rmd_local_cross_attn_workspace_bytes": (ctypes.c_size_t, [_I] * 5),
+    "rmd_local_cross_attn_backward": (_I, [_P, _P, _P, _P] + [_I] * 9 + [_P, _P, _P, _P, _P]),
     "rmd_sequence_loss_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
     "rmd_sequence_loss": (_I, [_P, _I, _P, _P] + [_I] * 6 + [ctypes.c_float, _P, _P, _P, _P]),
     "rmd_sequence_loss_backward": (_I, [_P, _I, _P, _P] + [_I] * 5 + [ctypes.c_float, _P, _P, _P]),

@@ -23,8 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _HEAD_SCHEMAS, _LOSS_SCHEMAS, _METRIC_SCHEMAS, _SCHEMAS, _STORAGE, check_head_args,
-                      check_loss_args, check_metric_args, pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
+from .library import (LIB, _ATTN_SCHEMAS, _HEAD_SCHEMAS, _LOSS_SCHEMAS, _METRIC_SCHEMAS, _SCHEMAS, _STORAGE,
+                      check_attn_args, check_head_args, check_loss_args, check_metric_args, pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
 def _delta(r, device):
@@ -519,6 +519,46 @@ def dicl_flow_head_backward(grad, cost, eps):
 _HEAD_KERNELS = {"dicl_flow_head": dicl_flow_head, "dicl_flow_head_backward": dicl_flow_head_backward}
 assert sorted(_HEAD_KERNELS) == sorted(_HEAD_SCHEMAS), "every rmd head operator needs a CPU kernel"
 
+# ---- hidden-state upsampler: local cross-attention (common/hsup.py:71-92) --------------------------
+
+def _window_views(t, window, h, w):
+    """(B, c, h2, w2) -> (B, c, wy*wx, h, w): the zero-padded window of every coarse cell, repeated over
+    the fine pixels of the cell (hsup.py:71-74, :76-79)."""
+    batch, c, h2, w2 = t.shape
+    n = window[0] * window[1]
+    t = F.unfold(t, kernel_size=window, padding=(window[0] // 2, window[1] // 2))
+    t = t.view(batch, c, n, h2, 1, w2, 1).expand(-1, -1, -1, -1, h // h2, -1, w // w2)
+    return t.reshape(batch, c, n, h, w)
+
+
+def local_cross_attn_eager(q, k, v, window=(3, 3)):
+    """The attention of HUpCrossAttn.forward, hsup.py:66-92, op for op -> (B, cv, h, w)."""
+    batch, ck, h, w = q.shape
+    n = window[0] * window[1]
+    k = _window_views(k, window, h, w)
+    v = _window_views(v, window, h, w)
+    k = k.permute(0, 3, 4, 1, 2)                                        # hsup.py:82-83
+    q = q.permute(0, 2, 3, 1).view(batch, h, w, 1, ck)
+    a = F.softmax(torch.matmul(q, k).squeeze(3), dim=-1)                # hsup.py:85-86
+    a = a.permute(0, 3, 1, 2).view(batch, 1, n, h, w)                   # hsup.py:89-90
+    return (a * v).sum(dim=2)                                           # hsup.py:92
+
+
+def local_cross_attn(q, k, v, win_y, win_x):
+    check_attn_args(q, k, v, win_y, win_x)
+    return local_cross_attn_eager(q.float(), k.float(), v.float(), (win_y, win_x))
+
+
+def local_cross_attn_backward(grad, q, k, v, win_y, win_x):
+    check_attn_args(q, k, v, win_y, win_x, grad)
+    with torch.enable_grad():
+        ins = [t.detach().float().requires_grad_(True) for t in (q, k, v)]
+        return torch.autograd.grad(local_cross_attn(*ins, win_y, win_x), ins, grad.float())
+
+
+_ATTN_KERNELS = {"local_cross_attn": local_cross_attn, "local_cross_attn_backward": local_cross_attn_backward}
+assert sorted(_ATTN_KERNELS) == sorted(_ATTN_SCHEMAS), "every rmd upsampler operator needs a CPU kernel"
+
 _KERNELS = {
     "corr_pyramid": corr_pyramid, "corr_lookup": corr_lookup,
     "corr_otf_prepare": corr_otf_prepare, "corr_otf_lookup": corr_otf_lookup,
@@ -531,6 +571,7 @@ _KERNELS = {
 }
 assert sorted(_KERNELS) == sorted(_SCHEMAS), "every rmd operator needs a CPU kernel"
 
-for _name, _fn in list(_KERNELS.items()) + list(_LOSS_KERNELS.items()) + list(_HEAD_KERNELS.items()):
+for _name, _fn in (list(_KERNELS.items()) + list(_LOSS_KERNELS.items()) + list(_HEAD_KERNELS.items())
+                   + list(_ATTN_KERNELS.items())):
     LIB.impl(_name, _fn, "CPU")
     LIB.impl(_name, _fn, "AutogradCPU")

@@ -20,6 +20,8 @@ is again an rmd operator.  Schemas follow SURVEY.md §8(b):
         (the loss operators, listed by loss_operators())                     raft_dicl_ctf_l3.py:430-473, dicl.py:436-472
   dicl_flow_head(cost, flow_coarse?, eps) -> (B, 3, h, w) flow + entropy     impls/dicl.py:31-85, 194-195, 202
         (the head operators, listed by head_operators())
+  local_cross_attn(q, k, v, win_y, win_x) -> (B, cv, h, w)                   common/hsup.py:71-92
+        (the upsampler operators, listed by attn_operators())
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -1033,6 +1035,114 @@ def _head_bwd(ctx, grad):
 torch.library.register_autograd("rmd::dicl_flow_head", _head_bwd, setup_context=_head_setup)
 
 
+# ---- hidden-state upsampler: local cross-attention -----------------------------------------------
+#
+# A fifth table: attn_operators().  local_cross_attn is the attention of HUpCrossAttn.forward
+# (common/hsup.py:71-92) without the expanded K / V; its autograd formula is local_cross_attn_backward,
+# which recomputes the softmax from q, k and v (nothing else is saved).
+
+_ATTN_SCHEMAS = {
+    "local_cross_attn": "local_cross_attn(Tensor q, Tensor k, Tensor v, int win_y, int win_x) -> Tensor",
+    "local_cross_attn_backward": ("local_cross_attn_backward(Tensor grad, Tensor q, Tensor k, Tensor v, int win_y, "
+                                  "int win_x) -> (Tensor, Tensor, Tensor)"),
+}
+for _s in _ATTN_SCHEMAS.values():
+    LIB.define(_s)
+
+ATTN_WINDOWS = (1, 3, 5)
+ATTN_MAX_FACTOR = 64
+
+
+def check_attn_args(q, k, v, win_y, win_x, grad=None):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of the attention operators."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f"local_cross_attn: q, k, v must be (B, c, h, w), got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    b, ck, h, w = q.shape
+    _, cv, h2, w2 = v.shape
+    if min(b, ck, h, w, cv, h2, w2) < 1:
+        raise ValueError(f"local_cross_attn: empty tensor (q {tuple(q.shape)}, v {tuple(v.shape)})")
+    if tuple(k.shape) != (b, ck, h2, w2) or v.shape[0] != b:
+        raise ValueError(f"local_cross_attn: k must be ({b}, {ck}, {h2}, {w2}) for q {tuple(q.shape)} and "
+                         f"v {tuple(v.shape)}, got {tuple(k.shape)}")
+    if win_y not in ATTN_WINDOWS or win_x not in ATTN_WINDOWS:
+        raise ValueError(f"local_cross_attn: window {win_y}x{win_x}: sizes must be in {ATTN_WINDOWS}")
+    if h % h2 or w % w2:
+        raise RuntimeError(f"local_cross_attn: the fine size of q {tuple(q.shape)} is not an integer multiple of the "
+                           f"coarse size of k {tuple(k.shape)}")
+    if h // h2 > ATTN_MAX_FACTOR or w // w2 > ATTN_MAX_FACTOR:
+        raise ValueError(f"local_cross_attn: factors {h // h2}x{w // w2} above {ATTN_MAX_FACTOR} are not supported")
+    if grad is not None and tuple(grad.shape) != (b, cv, h, w):
+        raise ValueError(f"local_cross_attn: grad must be ({b}, {cv}, {h}, {w}), got {tuple(grad.shape)}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("grad", grad)):
+        if t is not None and not t.is_floating_point():
+            raise ValueError(f"local_cross_attn: {name} must be a floating-point tensor, got {t.dtype}")
+
+
+def _local_cross_attn(q, k, v, win_y, win_x):
+    check_attn_args(q, k, v, win_y, win_x)
+    _all_gpu("local_cross_attn", q, k, v)
+    qc, kc, vc = _f32(q), _f32(k), _f32(v)
+    b, ck, h, w = qc.shape
+    _, cv, h2, w2 = vc.shape
+    out = torch.empty((b, cv, h, w), dtype=torch.float32, device=qc.device)
+    with _Dev(qc) as st:
+        _lib.check(_lib.lib().rmd_local_cross_attn(_ptr(qc), _ptr(kc), _ptr(vc), b, ck, cv, h, w, h2, w2, win_y, win_x,
+                                                   _ptr(out), st), "rmd_local_cross_attn")
+    return out
+
+
+LIB.impl("local_cross_attn", _local_cross_attn, "CUDA")
+
+
+@_fake("local_cross_attn")
+def _(q, k, v, win_y, win_x):
+    check_attn_args(q, k, v, win_y, win_x)
+    return q.new_empty((q.shape[0], v.shape[1], q.shape[2], q.shape[3]), dtype=torch.float32)
+
+
+def _local_cross_attn_backward(grad, q, k, v, win_y, win_x):
+    check_attn_args(q, k, v, win_y, win_x, grad)
+    _all_gpu("local_cross_attn_backward", grad, q, k, v)
+    g, qc, kc, vc = _f32(grad), _f32(q), _f32(k), _f32(v)
+    b, ck, h, w = qc.shape
+    _, cv, h2, w2 = vc.shape
+    gq, gk, gv = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
+    nbytes = _lib.lib().rmd_local_cross_attn_workspace_bytes(b, h, w, win_y, win_x)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=qc.device)
+    with _Dev(qc) as st:
+        _lib.check(_lib.lib().rmd_local_cross_attn_backward(_ptr(g), _ptr(qc), _ptr(kc), _ptr(vc), b, ck, cv, h, w, h2,
+                                                            w2, win_y, win_x, _ptr(gq), _ptr(gk), _ptr(gv), _ptr(ws),
+                                                            st), "rmd_local_cross_attn_backward")
+    return gq, gk, gv
+
+
+LIB.impl("local_cross_attn_backward", _local_cross_attn_backward, "CUDA")
+
+
+@_fake("local_cross_attn_backward")
+def _(grad, q, k, v, win_y, win_x):
+    check_attn_args(q, k, v, win_y, win_x, grad)
+    return tuple(t.new_empty(t.shape, dtype=torch.float32) for t in (q, k, v))
+
+
+def _attn_setup(ctx, inputs, output):
+    q, k, v, ctx.win_y, ctx.win_x = inputs
+    ctx.save_for_backward(q, k, v)
+
+
+def _attn_bwd(ctx, grad):
+    q, k, v = ctx.saved_tensors
+    if not any(ctx.needs_input_grad[:3]):
+        return None, None, None, None, None
+    grads = torch.ops.rmd.local_cross_attn_backward(grad, q, k, v, ctx.win_y, ctx.win_x)
+    return tuple(g.to(t.dtype) if need else None
+                 for g, t, need in zip(grads, (q, k, v), ctx.needs_input_grad[:3])) + (None, None)
+
+
+torch.library.register_autograd("rmd::local_cross_attn", _attn_bwd, setup_context=_attn_setup)
+
+
 def operators():
     """Names of the registered torch.ops.rmd model operators."""
     return sorted(_SCHEMAS)
@@ -1051,3 +1161,8 @@ def metric_operators():
 def head_operators():
     """Names of the registered torch.ops.rmd DICL flow-head operators."""
     return sorted(_HEAD_SCHEMAS)
+
+
+def attn_operators():
+    """Names of the registered torch.ops.rmd hidden-state upsampler (local cross-attention) operators."""
+    return sorted(_ATTN_SCHEMAS)

@@ -515,6 +515,15 @@ def dicl_flow_head(cost, flow_coarse=None, eps=1e-9):
     return out[:, :2], out[:, 2:]
 
 
+def local_cross_attn(q, k, v, window=(3, 3)):
+    """q (B, ck, h, w), k (B, ck, h2, w2), v (B, cv, h2, w2) -> (B, cv, h, w): every fine pixel attends over
+    the `window` of coarse cells around its parent cell, zero-padded at the border (the attention of
+    HUpCrossAttn.forward, common/hsup.py:71-92), in one pass without the expanded K / V."""
+    _same_device(q, k, v)
+    win_y, win_x = (int(s) for s in window)
+    return torch.ops.rmd.local_cross_attn(q, k, v, win_y, win_x)
+
+
 # ---- sequence losses -----------------------------------------------------------------------------
 
 LOSS_ORDS = {1: _lib.RMD_LOSS_L1, 2: _lib.RMD_LOSS_L2, "absmean": _lib.RMD_LOSS_ABSMEAN,
