@@ -36,10 +36,6 @@ namespace {
 constexpr int kThreads = 256;
 
 constexpr int kGcw = 8;                // targets per G chunk
-// lookup backward: 1 = read-modify-write whole 32-B chunk pieces as 16-B vectors, 0 = one float per target
-#ifndef RMD_BWD_VEC
-#define RMD_BWD_VEC 1
-#endif
 
 struct GradGeom {
     int batch, height, width, levels;
@@ -128,48 +124,40 @@ corr_lookup_backward_kernel(const float* __restrict__ gout, GradGeom g, const fl
         const int y = ys + j;
         if (y >= 0 && y < lh) {
             float* r = col + (size_t)y * g.nch[L] * chs;
-            if constexpr (RMD_BWD_VEC) {
-                // whole 32-B chunk pieces: the row's K values shifted to their in-chunk slots (a 3-stage
-                // barrel shift by xs mod 8), then each chunk the row touches read, added to and written as
-                // two 16-B vectors (the lane owns (chunk, query) for this launch: no other lane writes it);
-                // slots outside the window or past the level's width add 0
-                constexpr int NC = (K + 14) / 8, NW = 8 * NC;
-                float wv[NW];
+            // whole 32-B chunk pieces: the row's K values shifted to their in-chunk slots (a 3-stage
+            // barrel shift by xs mod 8), then each chunk the row touches read, added to and written as
+            // two 16-B vectors (the lane owns (chunk, query) for this launch: no other lane writes it);
+            // slots outside the window or past the level's width add 0
+            constexpr int NC = (K + 14) / 8, NW = 8 * NC;
+            float wv[NW];
 #pragma unroll
-                for (int i = 0; i < NW; ++i) wv[i] = i < K ? xlerp(qcur[i], qprev[i], fy) : 0.f;
-                const int sh = xs & 7;
+            for (int i = 0; i < NW; ++i) wv[i] = i < K ? xlerp(qcur[i], qprev[i], fy) : 0.f;
+            const int sh = xs & 7;
 #pragma unroll
-                for (int st = 1; st < 8; st <<= 1) {
-                    const bool on = (sh & st) != 0;
+            for (int st = 1; st < 8; st <<= 1) {
+                const bool on = (sh & st) != 0;
 #pragma unroll
-                    for (int i = NW - 1; i >= 0; --i) wv[i] = on ? (i >= st ? wv[i - st] : 0.f) : wv[i];
-                }
-                const int c0 = xs >> 3, nch = g.nch[L];
-                const int nc = (sh + K + 7) >> 3;                       // chunks this row spans (2 or 3 at r = 4)
+                for (int i = NW - 1; i >= 0; --i) wv[i] = on ? (i >= st ? wv[i - st] : 0.f) : wv[i];
+            }
+            const int c0 = xs >> 3, nch = g.nch[L];
+            const int nc = (sh + K + 7) >> 3;                       // chunks this row spans (2 or 3 at r = 4)
 #pragma unroll
-                for (int k = 0; k < NC; ++k) {
-                    const int c = c0 + k;
-                    if (k >= nc || c < 0 || c >= nch) continue;
-                    float4* pc = reinterpret_cast<float4*>(r + (size_t)c * chs);
-                    float4 a = pc[0], b = pc[1];
-                    const int lim = lw - 8 * c;                         // slots e < lim are on the level
-                    a.x += 0 < lim ? wv[8 * k + 0] : 0.f;
-                    a.y += 1 < lim ? wv[8 * k + 1] : 0.f;
-                    a.z += 2 < lim ? wv[8 * k + 2] : 0.f;
-                    a.w += 3 < lim ? wv[8 * k + 3] : 0.f;
-                    b.x += 4 < lim ? wv[8 * k + 4] : 0.f;
-                    b.y += 5 < lim ? wv[8 * k + 5] : 0.f;
-                    b.z += 6 < lim ? wv[8 * k + 6] : 0.f;
-                    b.w += 7 < lim ? wv[8 * k + 7] : 0.f;
-                    pc[0] = a;
-                    pc[1] = b;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < K; ++i) {
-                    const int x = xs + i;
-                    if (x >= 0 && x < lw) r[(size_t)(x >> 3) * chs + (x & 7)] += qcur[i] * (1.0f - fy) + qprev[i] * fy;
-                }
+            for (int k = 0; k < NC; ++k) {
+                const int c = c0 + k;
+                if (k >= nc || c < 0 || c >= nch) continue;
+                float4* pc = reinterpret_cast<float4*>(r + (size_t)c * chs);
+                float4 a = pc[0], b = pc[1];
+                const int lim = lw - 8 * c;                         // slots e < lim are on the level
+                a.x += 0 < lim ? wv[8 * k + 0] : 0.f;
+                a.y += 1 < lim ? wv[8 * k + 1] : 0.f;
+                a.z += 2 < lim ? wv[8 * k + 2] : 0.f;
+                a.w += 3 < lim ? wv[8 * k + 3] : 0.f;
+                b.x += 4 < lim ? wv[8 * k + 4] : 0.f;
+                b.y += 5 < lim ? wv[8 * k + 5] : 0.f;
+                b.z += 6 < lim ? wv[8 * k + 6] : 0.f;
+                b.w += 7 < lim ? wv[8 * k + 7] : 0.f;
+                pc[0] = a;
+                pc[1] = b;
             }
         }
 #pragma unroll
@@ -193,35 +181,19 @@ corr_lookup_backward_kernel(const float* __restrict__ gout, GradGeom g, const fl
 // corr_lookup_backward_kernel (xlerp) and adds them into the tile in lookup order.  Columns left or
 // right of the tile land in the trash slots.  The wave then stores the tile — lane l writes the 16 B
 // at byte 16 l of each 1-KB half of a (row, chunk)'s 2 KB, read across lanes, so every store
-// instruction covers 8 whole 128-B lines, non-temporal (G is 2 GB, read next by the GEMMs) — with pad
-// targets x >= W_l as 0, and clears it.  Each G element thus receives 0 + v_0 + v_1 + ... in lookup
-// order: the sum the sequential kernels form, bit for bit.  ACC: a tile starts from G's current
-// values (launches after the first when a forward holds more than kBuildMax lookups).
+// instruction covers 8 whole 128-B lines, non-temporal (G is 2 GB, read next by the GEMMs; streamed past
+// L2, which then keeps the grad_out / coordinate reads) — with pad targets x >= W_l as 0, and clears it.
+// Each G element thus receives 0 + v_0 + v_1 + ... in lookup order: the sum the sequential kernels form,
+// bit for bit.  ACC: a tile starts from G's current values (launches after the first when a forward
+// holds more than kBuildMax lookups).
 // Measured variants (profiles/grad_build_r05.json): register tiles with select-shifted accumulation,
 // one unit per wave, 1-row / 4-row tiles, lookup-at-a-time loads, a producer / consumer wave pair.
-#ifndef RMD_BUILD_ROWS
-#define RMD_BUILD_ROWS 2
-#endif
-#ifndef RMD_BUILD_CHUNKS
-#define RMD_BUILD_CHUNKS 4
-#endif
-// 1: G stores non-temporal (streamed past L2, which then keeps the grad_out / coordinate reads)
-#ifndef RMD_BUILD_NT
-#define RMD_BUILD_NT 1
-#endif
-// A/B ablations only: bit 0 sends every grad_out load out of range (no memory traffic, zeros)
-#ifndef RMD_BUILD_ABL
-#define RMD_BUILD_ABL 0
-#endif
-#ifndef RMD_BUILD_SEG
-#define RMD_BUILD_SEG 8
-#endif
-constexpr int kBuildMax = 16, kBuildRows = RMD_BUILD_ROWS, kBuildChunks = RMD_BUILD_CHUNKS, kBuildThreads = 64;
-constexpr int kBuildSegRows = RMD_BUILD_SEG * kBuildRows;     // target rows per wave (tiles in sequence)
-#ifndef RMD_BUILD_GROUP
-#define RMD_BUILD_GROUP 4
-#endif
-constexpr int kBuildGroup = RMD_BUILD_GROUP;                 // lookups per batch of loads
+// Tile 2 rows x 4 chunks, 8 tiles per segment, lookups in groups of 4: the fastest of the shapes swept
+// in profiles/grad_build_r05.json.
+constexpr int kBuildMax = 16, kBuildThreads = 64;
+constexpr int kBuildRows = 2, kBuildChunks = 4;              // tile: target rows x chunk columns
+constexpr int kBuildSegRows = 8 * kBuildRows;                // target rows per wave (8 tiles in sequence)
+constexpr int kBuildGroup = 4;                               // lookups per batch of loads
 constexpr int kBuildSlots = 8 * kBuildChunks + 2;            // tile columns + 2 trash slots
 constexpr unsigned kBuildOOB = 0x80000000u;                  // buffer offset past any slab: loads return 0
 
@@ -336,8 +308,7 @@ corr_grad_build_kernel(BuildArgs a, GradGeom g, float* __restrict__ grad) {
 #pragma unroll
                     for (int r = 0; r <= RB; ++r) {
                         const int jt = j0g[q] - 1 + r;
-                        const unsigned vo = act[q] && jt >= 0 && jt < D && !(RMD_BUILD_ABL & 1)
-                                                ? (unsigned)(jt * N + pc) * 4u : kBuildOOB;
+                        const unsigned vo = act[q] && jt >= 0 && jt < D ? (unsigned)(jt * N + pc) * 4u : kBuildOOB;
 #pragma unroll
                         for (int t = 0; t < D; ++t)
                             gt[q][r][t] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(
@@ -417,8 +388,7 @@ corr_grad_build_kernel(BuildArgs a, GradGeom g, float* __restrict__ grad) {
                                                                 (piece + lane) * kGcw);
                             const f32x4 o{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]),
                                           __uint_as_float(w[3])};
-                            if constexpr (RMD_BUILD_NT) __builtin_nontemporal_store(o, d);
-                            else *d = o;
+                            __builtin_nontemporal_store(o, d);
                         }
                     } else {
                         const int e0 = 4 * (lane & 1);
@@ -434,8 +404,7 @@ corr_grad_build_kernel(BuildArgs a, GradGeom g, float* __restrict__ grad) {
                             }
                             if (p0 + q < N) {
                                 f32x4* d = reinterpret_cast<f32x4*>(grad + (piece + q) * kGcw + e0);
-                                if constexpr (RMD_BUILD_NT) __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, d);
-                                else *d = f32x4{v[0], v[1], v[2], v[3]};
+                                __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, d);
                             }
                         }
                     }

@@ -341,25 +341,18 @@ struct Plan {
     int ntm, ntn, splits, kper, tn;
 };
 
-// output-tile width: 256 columns (A operand re-read half as often through L2) once the matrix is wide
+// output-tile width: kWideTN columns (A operand re-read half as often through L2) once the matrix is wide
 // enough, else 128
-#ifndef RMD_GG_TN
-#define RMD_GG_TN 256
-#endif
-inline int tile_n(int Nc) { return RMD_GG_TN == 256 && Nc >= 1024 ? 256 : 128; }
+constexpr int kWideTN = 256;
+inline int tile_n(int Nc) { return Nc >= 1024 ? kWideTN : 128; }
 
 // split count: the s minimising (workgroup rounds over 256 CUs) x (K chunks per split) plus the
 // workspace traffic of s > 1 in the same unit — each split writes an M x TN partial tile (kTM / kKC = 8
 // chunks' worth of operand reads) and the reduce reads s of them and writes one, at 1.5x a chunk's
 // cost per byte (profiles/grad_gemm_splits_r05.json: at cfg2 b8 this picks 1 and 2 splits where the
-// round-count-only rule picked 8 and 6, 1.12 vs 1.35 ms for the two GEMMs); a larger s must win by 3 %.
-// RMD_GG_MAXSPLIT caps s, RMD_GG_OLDPLAN=1 restores the round-4 rule (A/B builds).
-#ifndef RMD_GG_MAXSPLIT
-#define RMD_GG_MAXSPLIT 8
-#endif
-#ifndef RMD_GG_OLDPLAN
-#define RMD_GG_OLDPLAN 0
-#endif
+// round-count-only rule of round 4 picked 8 and 6, 1.12 vs 1.35 ms for the two GEMMs); a larger s must
+// win by 3 %.
+constexpr int kMaxSplit = 8;      // cap on s: the most the round-4 rule ever chose (same profile)
 Plan plan(int batch, int M, int K, int Nc) {
     Plan pl{};
     pl.tn = tile_n(Nc);
@@ -369,17 +362,9 @@ Plan plan(int batch, int M, int K, int Nc) {
     const int nch = (K + kKC - 1) / kKC;
     double best = 1e30;
     pl.splits = 1;
-    for (int s = 1; s <= RMD_GG_MAXSPLIT && s <= nch; ++s) {
+    for (int s = 1; s <= kMaxSplit && s <= nch; ++s) {
         const long long rounds = (tiles * s + 255) / 256;
         const int per = (nch + s - 1) / s;
-        if (RMD_GG_OLDPLAN) {
-            const double cost = (double)rounds * per + (s > 1 ? 0.15 * s * (double)tiles / 256.0 : 0.0);
-            if (cost < best - 1e-9) {
-                best = cost;
-                pl.splits = s;
-            }
-            continue;
-        }
         const double ws = s > 1 ? 1.5 * (kTM / kKC) * (2.0 * s + 1.0) * (double)tiles / 256.0 : 0.0;
         const double cost = (double)rounds * per + ws;
         if (cost < best * 0.97) {
@@ -408,7 +393,7 @@ void launch_gemm_tn(const GemmArgs& a, int nwg, bool x3, hipStream_t st) {
 
 template <bool VA, bool VB, int LAYOUT>
 void launch_gemm(const GemmArgs& a, int nwg, bool x3, int tn, hipStream_t st) {
-    if (tn == 256) launch_gemm_tn<VA, VB, LAYOUT, 256>(a, nwg, x3, st);
+    if (tn == kWideTN) launch_gemm_tn<VA, VB, LAYOUT, kWideTN>(a, nwg, x3, st);
     else launch_gemm_tn<VA, VB, LAYOUT, 128>(a, nwg, x3, st);
 }
 

@@ -28,20 +28,14 @@ namespace {
 constexpr int kThreads = 64;       // one wave per workgroup: 25.64 vs 25.89 us (256) in the bench
                                    // sequence (profiles/lookup_threads_r01.json)
 
-// A/B knob: the instruction-stream reductions of the BUF paths, one bit each (same loads, stores and
-// results in every combination; profiles/lookup_instr_r10.json):
-//   1  fp16 differences as v_fma_mix_f32 on the packed halves (no separate fp16 -> fp32 converts)
-//   2  barrel shift: the fp16 half-word step as one v_alignbit per word by a per-lane 0 / 16 bits
-//   8  (wave, level) invariants: 32-bit slab sizes, shifts for floor divisions, level / part without a
-//      division, running row and plane offsets instead of multiplies
-// (Bit 4 was the load offsets as one row select and one column mask per load instead of the `valid`
-// chains: 0.8 us slower cache-resident and 65-67 VGPRs; measured, dropped and removed.)
-#ifndef RMD_LOOKUP_DIET
-#define RMD_LOOKUP_DIET 11
-#endif
-constexpr bool kDietMix = (RMD_LOOKUP_DIET & 1) != 0, kDietBarrel = (RMD_LOOKUP_DIET & 2) != 0,
-               kDietHoist = (RMD_LOOKUP_DIET & 8) != 0;
-
+// The BUF paths carry three instruction-stream reductions (same loads, stores and results as the plain
+// forms; profiles/lookup_instr_r10.json):
+//  * fp16 differences as v_fma_mix_f32 on the packed halves (no separate fp16 -> fp32 converts);
+//  * barrel shift: the fp16 half-word step as one v_alignbit per word by a per-lane 0 / 16 bits;
+//  * (wave, level) invariants: 32-bit slab sizes, shifts for floor divisions, level / part without a
+//    division, running row and plane offsets instead of multiplies.
+// (Load offsets as one row select and one column mask per load instead of the `valid` chains were
+// 0.8 us slower cache-resident and 65-67 VGPRs; measured, dropped and removed.)
 
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -80,7 +74,7 @@ template <> __device__ __forceinline__ float word_elem<__half>(unsigned w, int i
 
 __device__ __forceinline__ int floor_div(int a, int d) { return a >= 0 ? a / d : -((d - 1 - a) / d); }
 
-// v1 - v0.  MIX (fp16 words, RMD_LOOKUP_DIET & 1): fma(v1, one, -v0) with an opaque one = 1.0f, so the
+// v1 - v0.  MIX (fp16 words of the BUF paths): fma(v1, one, -v0) with an opaque one = 1.0f, so the
 // fp16 -> fp32 converts of both values fold into a v_fma_mix_f32's operands; one rounding of the exact
 // difference either way, so the same bits.
 template <bool MIX>
@@ -97,7 +91,7 @@ __device__ __forceinline__ float opaque_one() {
 // Shift NW words (+1 zero word) left by sh elements of T (sh < TW): whole words in log steps, then a
 // half-word for fp16, and extract the K patch values with zero padding outside [0, lw) / bad rows.
 //
-// LEAN (the BUF paths, RMD_LOOKUP_DIET & 2): the half-word shift is one v_alignbit per word that holds
+// LEAN (the BUF paths): the half-word shift is one v_alignbit per word that holds
 // patch values, by a per-lane 0 or 16 bits — no select between the shifted and the unshifted word.
 // (The whole-word steps stay as they are: the compiler already drops the selects nothing reads, and
 // run from the largest step down it merges them into one compare per word and shift amount.)
@@ -171,30 +165,16 @@ template <typename T> constexpr bool kIsS24 = false;
 template <> constexpr bool kIsS24<s24_t> = true;
 
 template <typename T>
-__device__ __forceinline__ const T* level_base(const T* pyr, const PyrGeom& g, int L, int b) {
-    return pyr + g.off[L] + (long long)b * ((long long)g.ty[L] * g.tx[L] * g.slots * g.th[L] * g.tw[L]);
-}
-
-template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t level_rsrc(const T* pyr, const PyrGeom& g, int L, int b) {
-    if constexpr (kDietHoist) {
-        // the host checked per * sizeof(T) < 2^31 for every level: 32-bit products, one 32 x 32 -> 64 for b
-        const unsigned per = (unsigned)g.ty[L] * (unsigned)g.tx[L] * (unsigned)g.slots * (unsigned)(g.th[L] * g.tw[L]);
-        const unsigned char* base = reinterpret_cast<const unsigned char*>(pyr) + g.off[L] * (long long)sizeof(T) +
-                                    (unsigned long long)(unsigned)b * (per * (unsigned)sizeof(T));
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base);
-        const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<void*>(reinterpret_cast<const void*>(((uintptr_t)hi << 32) | lo)), (short)0,
-            (int)__builtin_amdgcn_readfirstlane(per * (unsigned)sizeof(T)), 0x00020000);
-    }
-    const long long per = (long long)g.ty[L] * g.tx[L] * g.slots * g.th[L] * g.tw[L];     // elements per image
-    const T* base = level_base(pyr, g, L, b);
+    // the host checked per * sizeof(T) < 2^31 for every level: 32-bit products, one 32 x 32 -> 64 for b
+    const unsigned per = (unsigned)g.ty[L] * (unsigned)g.tx[L] * (unsigned)g.slots * (unsigned)(g.th[L] * g.tw[L]);
+    const unsigned char* base = reinterpret_cast<const unsigned char*>(pyr) + g.off[L] * (long long)sizeof(T) +
+                                (unsigned long long)(unsigned)b * (per * (unsigned)sizeof(T));
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)base);
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uintptr_t)hi << 32) | lo), (short)0,
-                                             (int)__builtin_amdgcn_readfirstlane((unsigned)(per * sizeof(T))),
-                                             0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(reinterpret_cast<const void*>(((uintptr_t)hi << 32) | lo)), (short)0,
+        (int)__builtin_amdgcn_readfirstlane(per * (unsigned)sizeof(T)), 0x00020000);
 }
 
 template <int NW>
@@ -300,22 +280,15 @@ __device__ __forceinline__ OutBuf out_buf(float* o_block, int N, int D, int p, b
 template <int D>
 __device__ __forceinline__ void emit_row_buf(const OutBuf& ob, int N, int bb, float fy, const float (&hprev)[D],
                                              const float (&hcur)[D]) {
-    if constexpr (kDietHoist) {
-        // plane (a, bb) at (a * D + bb) * N * 4 bytes: one multiply per row, then adds of the D-plane stride
-        const unsigned dn4 = __builtin_amdgcn_readfirstlane((unsigned)(D * 4) * (unsigned)N);
-        unsigned so = __builtin_amdgcn_readfirstlane((unsigned)bb * (unsigned)N * 4u);
+    // plane (a, bb) at (a * D + bb) * N * 4 bytes: one multiply per row, then adds of the D-plane stride
+    const unsigned dn4 = __builtin_amdgcn_readfirstlane((unsigned)(D * 4) * (unsigned)N);
+    unsigned so = __builtin_amdgcn_readfirstlane((unsigned)bb * (unsigned)N * 4u);
 #pragma unroll
-        for (int a = 0; a < D; ++a) {
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(fmaf(fy, hcur[a] - hprev[a], hprev[a])), ob.rs,
-                                                  (int)ob.voff, (int)so, 2);
-            so += dn4;
-        }
-        return;
+    for (int a = 0; a < D; ++a) {
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(fmaf(fy, hcur[a] - hprev[a], hprev[a])), ob.rs,
+                                              (int)ob.voff, (int)so, 2);
+        so += dn4;
     }
-#pragma unroll
-    for (int a = 0; a < D; ++a)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(fmaf(fy, hcur[a] - hprev[a], hprev[a])), ob.rs, (int)ob.voff,
-                                              (int)__builtin_amdgcn_readfirstlane((unsigned)((a * D + bb) * N) * 4u), 2);
 }
 
 // Write the part's output rows: vertical interpolation of consecutive horizontally interpolated rows
@@ -374,12 +347,12 @@ __device__ __forceinline__ void rows_body_buf(__amdgpu_buffer_rsrc_t rs, const P
     constexpr int CB = CW * (int)sizeof(T);                         // chunk bytes
     constexpr int CWW = S24 ? CW : CB / 4;                          // chunk words (S24: widened)
     constexpr int NC = (K + CW - 1 + CW - 1) / CW;                  // chunks a row can span
-    constexpr bool MIX = kDietMix && std::is_same<TE, __half>::value;
+    constexpr bool MIX = std::is_same<TE, __half>::value;
     const int lh = g.lh[L], lw = g.lw[L], txs = g.tx[L];
     const unsigned cs = (unsigned)g.slots * CB, rsb = (unsigned)txs * cs;
     static_assert((CW & (CW - 1)) == 0, "chunk widths are powers of two");
-    const int tc0 = kDietHoist ? xs >> (CW == 8 ? 3 : (CW == 4 ? 2 : 1)) : floor_div(xs, CW);
-    const int sh = kDietHoist ? (xs & (CW - 1)) : xs - tc0 * CW;
+    const int tc0 = xs >> (CW == 8 ? 3 : (CW == 4 ? 2 : 1));             // floor(xs / CW)
+    const int sh = xs & (CW - 1);
     const unsigned off0 = (unsigned)tc0 * cs + (unsigned)slot * CB;  // wraps for tc0 < 0: used only when valid
     // (the chunk stride c * cs cannot go in the loads' scalar offset: the range check sees the vector
     // offset alone, which wraps below zero for a window that starts left of the level until c * cs is added)
@@ -391,7 +364,7 @@ __device__ __forceinline__ void rows_body_buf(__amdgpu_buffer_rsrc_t rs, const P
         const int j = bb0 + jj;
         const int yy = ys + j;
         const bool rv = yy >= 0 && yy < lh;
-        const unsigned roff = kDietHoist ? roff_run : off0 + (unsigned)yy * rsb;
+        const unsigned roff = roff_run;
         roff_run += rsb;
         unsigned wd[NC * CWW + 1];
 #pragma unroll
@@ -409,7 +382,7 @@ __device__ __forceinline__ void rows_body_buf(__amdgpu_buffer_rsrc_t rs, const P
         }
         wd[NC * CWW] = 0u;
         float v[K];
-        shift_extract<TE, K, CW, NC * CWW, MASK, kDietBarrel>(wd, sh, xs, lw, true, v);
+        shift_extract<TE, K, CW, NC * CWW, MASK, true>(wd, sh, xs, lw, true, v);
         float hcur[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) hcur[a] = fmaf(fx, diff_f32<MIX>(v[a + 1], v[a], one), v[a]);
@@ -483,7 +456,7 @@ __device__ __forceinline__ void tiles_body(const __half* __restrict__ pyr, const
     constexpr int NCR = KR / 2 + 1;                                 // chunk rows a part can span
     constexpr int NQ = (K + 3 + 3) / 4;                             // quads a patch row can span
     const int lh = g.lh[L], lw = g.lw[L];
-    constexpr bool HOIST = BUF && kDietHoist;
+    constexpr bool HOIST = BUF;                                     // shifts for the floor divisions
     const int ya = ys + bb0;
     const int cr0 = HOIST ? ya >> 1 : floor_div(ya, 2);
     const int par = HOIST ? (ya & 1) : ya - 2 * cr0;
@@ -538,7 +511,7 @@ __device__ __forceinline__ void tiles_body(const __half* __restrict__ pyr, const
         }
     }
 
-    constexpr bool MIX = BUF && kDietMix;
+    constexpr bool MIX = BUF;
     const float one = MIX ? opaque_one() : 1.0f;
     float hprev[D];
 #pragma unroll
@@ -564,7 +537,7 @@ __device__ __forceinline__ void tiles_body(const __half* __restrict__ pyr, const
         }
         rw[2 * NQ] = 0u;
         float v[K];
-        shift_extract<__half, K, 4, 2 * NQ, MASK, BUF && kDietBarrel>(rw, sh, xs, lw, row_ok, v);
+        shift_extract<__half, K, 4, 2 * NQ, MASK, BUF>(rw, sh, xs, lw, row_ok, v);
         float hcur[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) hcur[a] = fmaf(fx, diff_f32<MIX>(v[a + 1], v[a], one), v[a]);
@@ -601,22 +574,14 @@ __device__ __forceinline__ void lookup_level_tiles(const __half* __restrict__ py
 // grid: (slot blocks of 64, batch, level + levels * part) — one lane per (query slot, level, row part).
 // (Row parts adjacent in dispatch order, one XCD apart, and level 0 last measured no gain,
 // profiles/lookup_order_ab_r05.json.)
-#ifndef RMD_LOOKUP_WPE8
-#define RMD_LOOKUP_WPE8 0
-#endif
-#if RMD_LOOKUP_WPE8
-#define RMD_LOOKUP_ATTR __attribute__((amdgpu_waves_per_eu(8, 8)))
-#else
-#define RMD_LOOKUP_ATTR
-#endif
 template <typename T, int R, int PR, int LAY, bool BUF>
-__global__ void __launch_bounds__(kThreads) RMD_LOOKUP_ATTR
+__global__ void __launch_bounds__(kThreads)
 corr_lookup_kernel(const T* __restrict__ pyr, PyrGeom g, const float* __restrict__ coords, unsigned zmask,
                    float* __restrict__ out) {
     const int N = g.height * g.width;
     const int s = blockIdx.x * kThreads + threadIdx.x;
     int L, part;
-    if constexpr (BUF && kDietHoist) {
+    if constexpr (BUF) {
         // gridDim.z = 3 * levels (launch_lookup): z / levels and z % levels without the division
         const int z = (int)blockIdx.z;
         part = (z >= g.levels ? 1 : 0) + (z >= 2 * g.levels ? 1 : 0);
@@ -676,11 +641,8 @@ int launch_lookup(const void* pyr, const rmd_pyramid_desc& d, const float* coord
     const dim3 grid((g.slots + kThreads - 1) / kThreads, d.batch, d.levels * 3);
     const T* p = reinterpret_cast<const T*>(pyr);
     // buffer loads need every per-image level slab below 2^31 bytes (kOOB must lie past it); the
-    // pointer path stays for larger pyramids (-DRMD_LOOKUP_BUF=0 forces it for A/B builds)
-#ifndef RMD_LOOKUP_BUF
-#define RMD_LOOKUP_BUF 1
-#endif
-    bool buf = RMD_LOOKUP_BUF != 0;
+    // pointer path stays for larger pyramids
+    bool buf = true;
     for (int l = 0; l < d.levels; ++l)
         buf = buf && (double)d.tiles_y[l] * d.tiles_x[l] * d.query_slots * d.tile_h[l] * d.tile_w[l] * sizeof(T) <
                          2147483648.0;

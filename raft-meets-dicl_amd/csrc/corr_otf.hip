@@ -36,85 +36,28 @@ namespace rmd {
 namespace {
 
 constexpr int kThreads = 256;                        // prepare kernels
-// lookup workgroup size per compute (-D knobs)
-#ifndef RMD_OTF_NT_B
-#define RMD_OTF_NT_B 256
-#endif
-#ifndef RMD_OTF_NT_X
-#define RMD_OTF_NT_X 512
-#endif
-// wide-map bf16 query block (16 x WQY), workgroup size and occupancy hint (-D knobs for A/B builds)
-#ifndef RMD_OTF_WQY
-#define RMD_OTF_WQY 4
-#endif
-#ifndef RMD_OTF_WNT
-#define RMD_OTF_WNT 512
-#endif
-#ifndef RMD_OTF_WOCC
-#define RMD_OTF_WOCC 2
-#endif
 constexpr long long kWideBlocks = 4096;              // bf16: 16x4 query blocks from this many 16x2 blocks
 constexpr int kMaxTasks = 1024;                      // box segments of the MFMA path (more: per-query VALU)
-// Query block, occupancy and query-fragment placement per compute (-D knobs for A/B builds,
-// tools/_gpu_r03k.sh).  cfg2 bf16, one box per comparison (profiles/otf_patch_ab_r03.jsonl,
-// otf_ql_ab_r03.jsonl): 16x2 blocks with the query fragments in LDS (QL) 77.7 us; 16x1 with them in
-// registers 87.5; 16x4 in registers 84.8; 16x4 QL 100.7 at 256 threads, 77.2 at 512.  Round 4, with the
-// interleaved MFMA order (profiles/otf_put_ab_r04.json): bf16 16x2 QL 256 threads 69-71 us (16x4 at 512
-// 73-74, 16x1 88-91, 16x2 at 512 / 384 / 128 threads 75 / 86 / 83); split-bf16 16x2 QL 512 threads
-// 115-119 us (256 threads 136-139, register fragments 145-147).
-#ifndef RMD_OTF_QSX_B
-#define RMD_OTF_QSX_B 1
-#endif
-#ifndef RMD_OTF_QSY_B
-#define RMD_OTF_QSY_B 2
-#endif
-#ifndef RMD_OTF_QSX_X
-#define RMD_OTF_QSX_X 1
-#endif
-#ifndef RMD_OTF_QSY_X
-#define RMD_OTF_QSY_X 2
-#endif
-#ifndef RMD_OTF_OCC_B
-#define RMD_OTF_OCC_B 2
-#endif
-#ifndef RMD_OTF_OCC_X
-#define RMD_OTF_OCC_X 2
-#endif
-#ifndef RMD_OTF_QL_B
-#define RMD_OTF_QL_B 1
-#endif
-#ifndef RMD_OTF_QL_X
-#define RMD_OTF_QL_X 1
-#endif
-// LDS write of a task's products (put): 1 = every lane writes its 4 products, those outside its query's
-// patch into a pad slot (no branches), 0 = only the products inside, under per-element branches.
-// cfg2 A/B (profiles/otf_put_ab_r04.json): bf16 70.8-73.2 us with 1 vs 75.9-78.5 with 0; split-bf16
-// (two waves per SIMD) 150 with 0 vs 170 with 1
-#ifndef RMD_OTF_PUTSEL_B
-#define RMD_OTF_PUTSEL_B 1
-#endif
-#ifndef RMD_OTF_PUTSEL_X
-#define RMD_OTF_PUTSEL_X 0
-#endif
-// MFMA order in a task: 1 = load step outer, query segments inner (independent chains interleaved)
-#ifndef RMD_OTF_ILV
-#define RMD_OTF_ILV 1
-#endif
-// backward ablation for A/B timing only (wrong results): 1 = the dP atomic adds are skipped, 2 = the G
-// build reads no record weights (constants instead)
-#ifndef RMD_OTF_BWD_ABL
-#define RMD_OTF_BWD_ABL 0
-#endif
-// pad slots per query patch in LDS (odd patch stride): 1, or 4 = one per lane group (put's pad writes of
-// the 4 lane groups of a query go to distinct addresses)
-#ifndef RMD_OTF_PADS
-#define RMD_OTF_PADS 1
-#endif
-// ablation for A/B timing only (wrong results): 1 = no output stores, 2 = no MFMA tasks, 3 = tasks
-// without MFMAs (operand loads and puts), 4 = tasks without operand loads (MFMAs on one task's operands)
-#ifndef RMD_OTF_ABL
-#define RMD_OTF_ABL 0
-#endif
+// Lookup launch shape per compute: query block of qsx x qsy segments, workgroup threads, occupancy hint,
+// query fragments in LDS (ql) or in registers.  cfg2 bf16, one box per comparison
+// (profiles/otf_patch_ab_r03.jsonl, otf_ql_ab_r03.jsonl): 16x2 blocks with the query fragments in LDS
+// 77.7 us; 16x1 with them in registers 87.5; 16x4 in registers 84.8; 16x4 in LDS 100.7 at 256 threads,
+// 77.2 at 512.  Round 4, with the interleaved MFMA order (profiles/otf_put_ab_r04.json): bf16 16x2 LDS
+// 256 threads 69-71 us (16x4 at 512 73-74, 16x1 88-91, 16x2 at 512 / 384 / 128 threads 75 / 86 / 83);
+// split-bf16 16x2 LDS 512 threads 115-119 us (256 threads 136-139, register fragments 145-147).
+struct LookShape {
+    int qsx, qsy, threads, occ;
+    bool ql;
+};
+constexpr LookShape kShapeBf16{1, 2, 256, 2, true};
+constexpr LookShape kShapeWide{1, 4, 512, 2, true};  // bf16 on wide maps (kWideBlocks; figures at the dispatch)
+constexpr LookShape kShapeSplit{1, 2, 512, 2, true};
+constexpr LookShape kShapeF32{1, 2, 256, 1, false};  // f32: query fragments in registers
+// LDS write of a task's products (put): true = every lane writes its 4 products, those outside its query's
+// patch into a pad slot (no branches), false = only the products inside, under per-element branches.
+// cfg2 A/B (profiles/otf_put_ab_r04.json): bf16 70.8-73.2 us with true vs 75.9-78.5 with false; split-bf16
+// (two waves per SIMD) 150 with false vs 170 with true; f32 goes with split-bf16
+constexpr bool kPutSelBf16 = true, kPutSelSplit = false;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -285,8 +228,8 @@ __device__ __forceinline__ void seg_mma(f32x4& acc, const typename Seg<T>::frag*
 // load each target segment of their box once for more queries (the L2 -> CU operand traffic is the
 // bound: every block re-reads its box), at the cost of MFMA tiles for targets outside a query's own
 // window.  A 16 x 4 block (bf16) reads 2.5x fewer target bytes per query than 16 x 2.
-// LDS floats per query patch: the (2r+2)^2 products, then RMD_OTF_PADS pad slots, rounded to an odd stride
-constexpr int otf_patch_stride(int R) { return ((2 * R + 2) * (2 * R + 2) + RMD_OTF_PADS) | 1; }
+// LDS floats per query patch: the (2r+2)^2 products, then the pad slot of put, rounded to an odd stride
+constexpr int otf_patch_stride(int R) { return ((2 * R + 2) * (2 * R + 2) + 1) | 1; }
 
 template <int QSX, int QSY> struct QBlock {
     static constexpr int kQS = QSX * QSY, kBX = 16 * QSX, kBY = QSY, kQ = kBX * kBY;
@@ -306,7 +249,7 @@ otf_lookup_kernel(const T* __restrict__ qseg, const T* __restrict__ tseg, OtfGeo
     constexpr int kQS = QB::kQS, kBX = QB::kBX, kBY = QB::kBY, kQ = QB::kQ;
     constexpr int kWaves = kLookThreads / 64;
     constexpr int D = 2 * R + 1, K = 2 * R + 2, KK = K * K, KKp = otf_patch_stride(R);   // odd: queries spread over banks
-    constexpr bool kPutSel = sizeof(T) == 2 && !X3 ? RMD_OTF_PUTSEL_B != 0 : RMD_OTF_PUTSEL_X != 0;
+    constexpr bool kPutSel = sizeof(T) == 2 && !X3 ? kPutSelBf16 : kPutSelSplit;
     extern __shared__ float S[];                       // [kQ][KKp]: every query's (2r+2)^2 patch
     // every level's window origins / fractions and the block's bounding box per level, computed once
     // before the level loop (no per-level reduction barriers)
@@ -437,9 +380,8 @@ otf_lookup_kernel(const T* __restrict__ qseg, const T* __restrict__ tseg, OtfGeo
                 const bool rok = (unsigned)dy < (unsigned)K;
                 float* P = S + wq[s] * KKp;
                 if constexpr (kPutSel) {
-                    const int pad = KK + (RMD_OTF_PADS > 1 ? (lane >> 4) % RMD_OTF_PADS : 0);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) P[rok && (unsigned)(dx0 + e) < (unsigned)K ? dy * K + dx0 + e : pad] = acc[e];
+                    for (int e = 0; e < 4; ++e) P[rok && (unsigned)(dx0 + e) < (unsigned)K ? dy * K + dx0 + e : KK] = acc[e];
                 } else if (rok) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
@@ -460,50 +402,24 @@ otf_lookup_kernel(const T* __restrict__ qseg, const T* __restrict__ tseg, OtfGeo
             };
             if constexpr (CPT > 0) {
                 frag tc[NLS];
-                if constexpr (RMD_OTF_ABL == 4) {          // ablation: one task's operands for all tasks
-                    const T* tsb = tptr(by0, sa);
+                for (int task = w; task < ntask; task += kWaves, advance(tr, tcol)) {
+                    const T* tsb = tptr(tr, tcol);
 #pragma unroll
                     for (int ls = 0; ls < NLS; ++ls) tc[ls] = *reinterpret_cast<const frag*>(tsb + (size_t)ls * 64 * SG::LE);
-                }
-                for (int task = w; task < (RMD_OTF_ABL == 2 ? 0 : ntask); task += kWaves, advance(tr, tcol)) {
-                    if constexpr (RMD_OTF_ABL != 4) {
-                        const T* tsb = tptr(tr, tcol);
+                    // load step outer, query segment inner: kQS independent accumulator chains interleave
+                    f32x4 acc[kQS];
 #pragma unroll
-                        for (int ls = 0; ls < NLS; ++ls) tc[ls] = *reinterpret_cast<const frag*>(tsb + (size_t)ls * 64 * SG::LE);
-                    }
-                    if constexpr (RMD_OTF_ILV && RMD_OTF_ABL != 3) {
-                        // load step outer, query segment inner: kQS independent accumulator chains interleave
-                        f32x4 acc[kQS];
+                    for (int s = 0; s < kQS; ++s) acc[s] = f32x4{};
 #pragma unroll
-                        for (int s = 0; s < kQS; ++s) acc[s] = f32x4{};
+                    for (int ls = 0; ls < NLS; ls += NP)
 #pragma unroll
-                        for (int ls = 0; ls < NLS; ls += NP)
-#pragma unroll
-                            for (int s = 0; s < kQS; ++s) {
-                                frag u[NP];
-                                qget(u, s, ls);
-                                seg_mma<T, X3>(acc[s], tc + ls, u);
-                            }
-#pragma unroll
-                        for (int s = 0; s < kQS; ++s) put(acc[s], s, tr, tcol);
-                    } else {
-#pragma unroll
-                    for (int s = 0; s < kQS; ++s) {
-                        f32x4 acc = {};
-                        if constexpr (RMD_OTF_ABL == 3) {      // ablation: operand loads and puts, no MFMA
-#pragma unroll
-                            for (int ls = 0; ls < NLS; ++ls) acc[ls & 3] += (float)tc[ls][s & 7];
-                        } else {
-#pragma unroll
-                            for (int ls = 0; ls < NLS; ls += NP) {
-                                frag u[NP];
-                                qget(u, s, ls);
-                                seg_mma<T, X3>(acc, tc + ls, u);
-                            }
+                        for (int s = 0; s < kQS; ++s) {
+                            frag u[NP];
+                            qget(u, s, ls);
+                            seg_mma<T, X3>(acc[s], tc + ls, u);
                         }
-                        put(acc, s, tr, tcol);
-                    }
-                    }
+#pragma unroll
+                    for (int s = 0; s < kQS; ++s) put(acc[s], s, tr, tcol);
                 }
             } else {
                 for (int task = w; task < ntask; task += kWaves, advance(tr, tcol)) {
@@ -579,7 +495,6 @@ otf_lookup_kernel(const T* __restrict__ qseg, const T* __restrict__ tseg, OtfGeo
             const int y = qy0 + q / kBX, x = qx0 + q % kBX;
             if (y >= g.H || x >= g.W) continue;
             const float fy = sfy[L][q] + (sfx[L][q] - sfx[L][q]);   // a NaN x weight reaches rows outside the band too
-            if (RMD_OTF_ABL == 1 && fy != 12345.f) continue;
             float* o = ob + (size_t)(a * D) * N + y * g.W + x;
 #pragma unroll
             for (int bb = 0; bb < D; ++bb) o[(size_t)bb * N] = fmaf(fy, hx[i][bb + 1] - hx[i][bb], hx[i][bb]);
@@ -972,9 +887,7 @@ otf_backward_kernel(BwdArgs a) {
                                 const int tx = o.x + k;
                                 const int si = (tx >> 4) - brow_x0[br];
                                 const bool ok = rok && k < K && tx >= 0 && tx < lw && si >= 0 && si < brow_n[br];
-                                v[ri][br][m] = ok ? (RMD_OTF_BWD_ABL == 2 ? 1e-3f * (float)(k + jr)
-                                                                          : wq[(size_t)(jr * K + k) * N])
-                                                  : 0.f;
+                                v[ri][br][m] = ok ? wq[(size_t)(jr * K + k) * N] : 0.f;
                             }
                         }
                     }
@@ -1083,7 +996,7 @@ otf_backward_kernel(BwdArgs a) {
                             if (s >= nseg) continue;
                             const int tx = bseg_x[s] * 16 + (jt & 15);
                             const float val = accp[t][v];
-                            if (tx >= lw || val == 0.f || RMD_OTF_BWD_ABL == 1) continue;
+                            if (tx >= lw || val == 0.f) continue;
                             const size_t e = ((size_t)b * a.pT + a.poff[l] + (size_t)bseg_row[s] * lw + tx) * g.C + ch;
                             if (__builtin_isfinite(val))
                                 atomicAdd(reinterpret_cast<unsigned long long*>(a.dP + e),
@@ -1257,40 +1170,39 @@ extern "C" int rmd_corr_otf_lookup(const void* workspace, int batch, int channel
     const bool exact = compute == RMD_F32;
     const bool x3 = compute == RMD_BF16X3;
     const int cpt = (exact && g.Cp >= 128) || g.Cp > 256 ? 0 : g.Cp;
-    // query block per compute: bf16 QSX_B x QSY_B segments, split-bf16 / f32 QSX_X x QSY_X (query
-    // fragments in registers: 8 (bf16) / 16 (x3) load steps per segment at C = 256)
-#define RMD_OTF(T, RR, CC, QX, QY, OC)                                                                         \
+    // launch shape SH per compute (LookShape)
+#define RMD_OTF(T, RR, CC, SH)                                                                                 \
     do {                                                                                                       \
-        using QB = QBlock<QX, QY>;                                                                             \
-        auto k = otf_lookup_kernel<T, XS, RR, CC, QX, QY, OC, QLK, NTK>;                                        \
+        using QB = QBlock<SH.qsx, SH.qsy>;                                                                     \
+        auto k = otf_lookup_kernel<T, XS, RR, CC, SH.qsx, SH.qsy, SH.occ, SH.ql, SH.threads>;                   \
         const long long nblk = (long long)((width + QB::kBX - 1) / QB::kBX) * ((height + QB::kBY - 1) / QB::kBY) * batch; \
         RMD_REQUIRE(nblk < (1ll << 31), RMD_ERR_SHAPE, "rmd_corr_otf_lookup: grid too large");                  \
         const size_t lds = sizeof(float) * QB::kQ * otf_patch_stride(RR) +                      \
-                           (QLK && CC > 0 ? (size_t)QB::kQS * 16 * CC * XN * sizeof(T) : 0);                    \
+                           (SH.ql && CC > 0 ? (size_t)QB::kQS * 16 * CC * XN * sizeof(T) : 0);                  \
         RMD_REQUIRE(lds <= 160 * 1024, RMD_ERR_SHAPE, "rmd_corr_otf_lookup: %zu B of LDS per block", lds);      \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                   (int)lds);                                                                   \
         const T* q = reinterpret_cast<const T*>(workspace);                                                    \
-        k<<<(unsigned)nblk, NTK, lds, st>>>(q, q + qn * XN, g, coords, zero_level_mask, out);                   \
+        k<<<(unsigned)nblk, SH.threads, lds, st>>>(q, q + qn * XN, g, coords, zero_level_mask, out);            \
     } while (0)
-#define RMD_OTF_C(T, RR, QX, QY, OC)                                 \
-    switch (cpt) {                                                   \
-        case 32: RMD_OTF(T, RR, 32, QX, QY, OC); break;              \
-        case 64: RMD_OTF(T, RR, 64, QX, QY, OC); break;              \
-        case 128: RMD_OTF(T, RR, 128, QX, QY, OC); break;            \
-        case 256: RMD_OTF(T, RR, 256, QX, QY, OC); break;            \
-        default: RMD_OTF(T, RR, 0, QX, QY, OC); break;               \
+#define RMD_OTF_C(T, RR, SH)                                 \
+    switch (cpt) {                                           \
+        case 32: RMD_OTF(T, RR, 32, SH); break;              \
+        case 64: RMD_OTF(T, RR, 64, SH); break;              \
+        case 128: RMD_OTF(T, RR, 128, SH); break;            \
+        case 256: RMD_OTF(T, RR, 256, SH); break;            \
+        default: RMD_OTF(T, RR, 0, SH); break;               \
     }
-#define RMD_OTF_R(T, QX, QY, OC)                                     \
-    switch (radius) {                                                \
-        case 1: RMD_OTF_C(T, 1, QX, QY, OC); break;                  \
-        case 2: RMD_OTF_C(T, 2, QX, QY, OC); break;                  \
-        case 3: RMD_OTF_C(T, 3, QX, QY, OC); break;                  \
-        case 4: RMD_OTF_C(T, 4, QX, QY, OC); break;                  \
-        case 5: RMD_OTF_C(T, 5, QX, QY, OC); break;                  \
-        case 6: RMD_OTF_C(T, 6, QX, QY, OC); break;                  \
-        case 7: RMD_OTF_C(T, 7, QX, QY, OC); break;                  \
-        default: RMD_OTF_C(T, 8, QX, QY, OC); break;                 \
+#define RMD_OTF_R(T, SH)                                     \
+    switch (radius) {                                        \
+        case 1: RMD_OTF_C(T, 1, SH); break;                  \
+        case 2: RMD_OTF_C(T, 2, SH); break;                  \
+        case 3: RMD_OTF_C(T, 3, SH); break;                  \
+        case 4: RMD_OTF_C(T, 4, SH); break;                  \
+        case 5: RMD_OTF_C(T, 5, SH); break;                  \
+        case 6: RMD_OTF_C(T, 6, SH); break;                  \
+        case 7: RMD_OTF_C(T, 7, SH); break;                  \
+        default: RMD_OTF_C(T, 8, SH); break;                 \
     }
     // bf16 on wide maps (at least kWideBlocks 16x2 query blocks): 16x4 blocks at 512 threads read 45 %
     // fewer target bytes per query; at the 4K map (b2, 270x480) 362 us vs 396 us per lookup, at cfg2
@@ -1299,27 +1211,19 @@ extern "C" int rmd_corr_otf_lookup(const void* workspace, int batch, int channel
     if (compute == RMD_BF16 && blocks16x2 >= kWideBlocks) {
         constexpr bool XS = false;
         constexpr size_t XN = 1;
-        constexpr bool QLK = true;
-        constexpr int NTK = RMD_OTF_WNT;
-        RMD_OTF_R(__bf16, 1, RMD_OTF_WQY, RMD_OTF_WOCC)
+        RMD_OTF_R(__bf16, kShapeWide)
     } else if (compute == RMD_BF16) {
         constexpr bool XS = false;
         constexpr size_t XN = 1;
-        constexpr bool QLK = RMD_OTF_QL_B != 0;
-        constexpr int NTK = RMD_OTF_NT_B;
-        RMD_OTF_R(__bf16, RMD_OTF_QSX_B, RMD_OTF_QSY_B, RMD_OTF_OCC_B)
+        RMD_OTF_R(__bf16, kShapeBf16)
     } else if (x3) {
         constexpr bool XS = true;
         constexpr size_t XN = 2;                    // query segments: qn split pairs
-        constexpr bool QLK = RMD_OTF_QL_X != 0;
-        constexpr int NTK = RMD_OTF_NT_X;
-        RMD_OTF_R(__bf16, RMD_OTF_QSX_X, RMD_OTF_QSY_X, RMD_OTF_OCC_X)
+        RMD_OTF_R(__bf16, kShapeSplit)
     } else {
         constexpr bool XS = false;
         constexpr size_t XN = 1;
-        constexpr bool QLK = false;
-        constexpr int NTK = 256;
-        RMD_OTF_R(float, RMD_OTF_QSX_X, RMD_OTF_QSY_X, 1)
+        RMD_OTF_R(float, kShapeF32)
     }
 #undef RMD_OTF_R
 #undef RMD_OTF_C

@@ -445,8 +445,8 @@ __device__ __forceinline__ void s_mma(f32x16 (&acc)[NT], const bf16x8 (&bq)[16],
 
 // Every store is unconditional: an invalid one (query past N, row or chunk outside a level, a
 // level beyond g.levels) is redirected to this lane's 16-B trash slot, so each tile issues exactly
-// kStores stores (see s_load_b_asm).  ABL is a diagnostic ablation (RMD_ABLATE env): 1 = every
-// store to trash (no HBM write traffic).
+// kStores stores (see s_load_b_asm).  ABL is a diagnostic ablation (the product instantiates 0): 1 =
+// every store to trash (no HBM write traffic).
 // trash: this lane's slot in store-slot 0; slot k (a distinct 1 KiB line set per store of the
 // tile) keeps ABL = 1 stores from being merged by the compiler (the store count must stay exact)
 template <int ABL>
@@ -552,7 +552,7 @@ __device__ __forceinline__ void s_epilogue(const f32x16 (&acc)[4 * TH], const SC
     }
 }
 
-// ABL (diagnostic, RMD_ABLATE env): 0 = normal, 1 = every store to trash, 2 = no MFMA
+// ABL (diagnostic; the product instantiates 0): 0 = normal, 1 = every store to trash, 2 = no MFMA
 template <int TH, int ABL>
 __global__ void __launch_bounds__(STraits<TH>::kThreads, 1)
 corr_pyramid_stationary(const __bf16* __restrict__ opA, const __bf16* __restrict__ opB, PyrGeom g, int qsplit,
@@ -719,13 +719,10 @@ struct EpiState {
 // Epilogue piece s (0..15) of one tile, from accumulator set `acc`: level-0 chunk row m = s/2 of
 // column group tc = s%2, the level-1 sums of those rows, and every 4th / 8th / 16th piece the level-1
 // / level-2 / level-3 stores — so the pieces can ride along the k-steps of the next tile.
-// A/B knob (tools/build_variant.sh; the product build uses the default): RMD_W8_AUXH = cache-policy
-// bits of the level 1-3 stores (-1: the same as level 0's AUX)
-#ifndef RMD_W8_AUXH
-#define RMD_W8_AUXH -1
-#endif
+// Cache-policy bits of the level 1-3 stores: the same as level 0's AUX (temporal stores there: lookups
+// 26.0 vs 27.6 us but the GEMM 0.258-0.274 vs 0.211 ms, profiles/w8_store_policy_ab_r06.json).
 template <int AUX>
-constexpr int kAuxUpper = RMD_W8_AUXH < 0 ? AUX : RMD_W8_AUXH;
+constexpr int kAuxUpper = AUX;
 
 template <int S, int AUX>
 __device__ __forceinline__ void epi_piece(const f32x16 (&acc)[8], const Ctx& c, const LaneOff& lo, EpiState& st) {

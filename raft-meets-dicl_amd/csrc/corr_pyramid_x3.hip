@@ -13,9 +13,9 @@
 // each wave sweeps its own 32-query tiles (8 M-tiles of 16 targets x 2 N-tiles of 16 queries x 8
 // k-steps x 3 products), then pools in-lane and stores all four levels straight from the
 // accumulators with range-checked buffer stores (rows past the level fall outside the descriptor,
-// chunks past the row get a 1 GiB bias), as fp32 or as RMD_S24 (3-byte) values (epilogue16_s24, round
-// 6).  Partial last rounds of one-CU workgroups are balanced by splitting the remaining blocks' query
-// tiles (X3Sched).  The 32x32x16 form of rounds 2-4 is in git history (commit db30b41 and before;
+// chunks past the row get a 1 GiB bias), as fp32 (epilogue16) or as RMD_S24 (3-byte) values
+// (epilogue16_s24).  Partial last rounds of one-CU workgroups are balanced by splitting the remaining
+// blocks' query tiles (X3Sched).  The 32x32x16 form of rounds 2-4 is in git history (commit db30b41 and before;
 // profiles/x3_ab_r05.json compares them).
 
 #include "rmd_common.h"
@@ -169,21 +169,9 @@ __device__ __forceinline__ void swapf(float& x, float& y) {
 constexpr int AUX_NT = 2;     // non-temporal stores: the pyramid is re-read a whole GEMM later
 
 typedef __attribute__((ext_vector_type(3))) int i32x3;
-// RMD_S24 (include/rmd.h): a float rounded to its top 24 bits (round half away from zero on the
-// magnitude; a NaN stays a quiet NaN), kept in bytes 1..3 of the returned word
-__device__ __forceinline__ unsigned s24_round(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) : u + 0x80u;
-}
-// 4 floats -> the 12 bytes of their S24 values (3 words)
-__device__ __forceinline__ i32x3 pack24(float a, float b, float c, float d) {
-    const unsigned v0 = s24_round(a), v1 = s24_round(b), v2 = s24_round(c), v3 = s24_round(d);
-    return i32x3{(int)__builtin_amdgcn_perm(v1, v0, 0x05030201u), (int)__builtin_amdgcn_perm(v2, v1, 0x06050302u),
-                 (int)__builtin_amdgcn_perm(v3, v2, 0x07060503u)};
-}
-
-// RMD_S24 rounding of a value the x3 GEMM produces: u + 0x80, top 24 bits.  The general rule
-// (s24_round) keeps a NaN a NaN by OR-ing the quiet bit; here every NaN is an MFMA result from bf16
+// RMD_S24 (include/rmd.h: a float rounded to its top 24 bits, round half away from zero on the magnitude,
+// kept in bytes 1..3 of the word) for a value the x3 GEMM produces: u + 0x80, top 24 bits.  The general
+// rule keeps a NaN a NaN by OR-ing the quiet bit; here every NaN is an MFMA result from bf16
 // operands (payload = a bf16 NaN's, low 16 bits zero, quiet) or the default quiet NaN, passed through
 // v_add / v_mul of the pooling (which keep an input NaN's payload) — so the + 0x80 never carries out of
 // the low byte and u + 0x80 has the same top 24 bits as u | 0x00400000: one VALU op instead of five
@@ -204,27 +192,8 @@ __device__ __forceinline__ void swap16(unsigned& x, unsigned& y) {
     y = r[1];
 }
 
-// A/B knob (tools/build_variant.sh -D...; the product build uses the default): RMD_X3_ABL = the
-// kernel's ablation (1 = drop every store through a zero descriptor range; 2 = no epilogue, the
-// phase barriers kept; 3 = no epilogue and no barriers: timing only)
-#ifndef RMD_X3_ABL
-#define RMD_X3_ABL 0
-#endif
-// RMD_X3_FREE: 1 (product since round 6) = no ping-pong phase barriers, the two waves of a SIMD run
-// free; 0 = waves w and w + 4 alternate MFMA and epilogue phases between workgroup barriers.  With the
-// round-5 epilogue (~875 VALU per tile) the phases had to be separated; with epilogue16_s24 (~280) the
-// barriers cost more than they hide: cfg2 0.464-0.466 vs 0.477-0.479 ms in the bench step, GRBM cycles
-// 6.89M vs 7.42M, MFMA busy 0.69 vs 0.64 (profiles/x3_free_ab_r06.json)
-#ifndef RMD_X3_FREE
-#define RMD_X3_FREE 1
-#endif
-// RMD_X3_S24_R05 = 1: the round-5 S24 epilogue (epilogue16<true>) instead of epilogue16_s24 (A/B only)
-#ifndef RMD_X3_S24_R05
-#define RMD_X3_S24_R05 0
-#endif
-
 // ---- GEMM kernel (16x16x32 MFMA) ------------------------------------------------------------------
-// One workgroup (8 waves, two per SIMD, free-running: RMD_X3_FREE) owns an 8 x 16 target block; its waves
+// One workgroup (8 waves, two per SIMD, free-running) owns an 8 x 16 target block; its waves
 // sweep their own 32-query tiles through a B-fragment register ring, with v_mfma_f32_16x16x32_bf16 tiles:
 // a wave's 32-query tile is 2 N-tiles of 16 queries against 8 M-tiles of 16 targets (M-tile mt = 2 rp
 // + ch: rows 2rp, 2rp+1 x cols 8ch..8ch+7 of the block), 8 k-steps of 32 channels, each k-step in two
@@ -292,28 +261,19 @@ __device__ __forceinline__ void ksteps16(f32x4 (&acc)[8][2], bf16x8 (&acur)[8], 
     }
 }
 
-// Epilogue of one 32-query tile in the 16x16 layout: acc[mt][u][e] is, for lane (n, g) and query
+// F32 epilogue of one 32-query tile in the 16x16 layout: acc[mt][u][e] is, for lane (n, g) and query
 // 16 u + n, the target (row 2 rp + (g >> 1), col 8 ch + 4 (g & 1) + e) with mt = 2 rp + ch.
-// S24: RMD_S24 storage (3 bytes per element; the Lvl strides are in those bytes): lanes gather whole
-// 12-byte pieces (4 values) before each store.
-template <bool S24>
 __device__ __forceinline__ void epilogue16(const f32x4 (&acc)[8][2], const Lvl (&L)[4], int qt, int N, int n, int g) {
-    constexpr unsigned E = S24 ? 3u : 4u;                  // bytes per element
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const unsigned q = (unsigned)min(qt * 32 + 16 * u + n, N - 1);
-        // level 0: 1 x 8 chunks (8E bytes per query); lanes g = 2 r', 2 r' + 1 write row r' halves
+        // level 0: 1 x 8 chunks (32 bytes per query); lanes g = 2 r', 2 r' + 1 write row r' halves
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) {
-            const unsigned o = q * 8u * E + 4u * E * (g & 1) + soff(L[0], 2 * (mt >> 1) + (g >> 1), mt & 1);
-            if constexpr (S24) {
-                __builtin_amdgcn_raw_buffer_store_b96(pack24(acc[mt][u][0], acc[mt][u][1], acc[mt][u][2], acc[mt][u][3]),
-                                                      L[0].rsrc, (int)o, 0, AUX_NT);
-            } else {
-                const i32x4 d = {__float_as_int(acc[mt][u][0]), __float_as_int(acc[mt][u][1]),
-                                 __float_as_int(acc[mt][u][2]), __float_as_int(acc[mt][u][3])};
-                __builtin_amdgcn_raw_buffer_store_b128(d, L[0].rsrc, (int)o, 0, AUX_NT);
-            }
+            const unsigned o = q * 32u + 16u * (g & 1) + soff(L[0], 2 * (mt >> 1) + (g >> 1), mt & 1);
+            const i32x4 d = {__float_as_int(acc[mt][u][0]), __float_as_int(acc[mt][u][1]),
+                             __float_as_int(acc[mt][u][2]), __float_as_int(acc[mt][u][3])};
+            __builtin_amdgcn_raw_buffer_store_b128(d, L[0].rsrc, (int)o, 0, AUX_NT);
         }
         // level 1: horizontal pairs in-lane, vertical pairs across the lane halves (ch 0 lands in the lower,
         // ch 1 in the upper half): lane g then holds level-1 cols 2g, 2g+1 of level-1 row rp
@@ -326,65 +286,30 @@ __device__ __forceinline__ void epilogue16(const f32x4 (&acc)[8][2], const Lvl (
             swapf(x0, y0);
             swapf(x1, y1);
             const float s0 = x0 + y0, s1 = x1 + y1;
-            if constexpr (S24) {
-                // even g takes its odd neighbour's two columns (lane + 16): cols 2g .. 2g + 3 in one piece
-                const float s2 = __shfl_xor(s0, 16), s3 = __shfl_xor(s1, 16);
-                __builtin_amdgcn_raw_buffer_store_b96(
-                    pack24(0.25f * s0, 0.25f * s1, 0.25f * s2, 0.25f * s3), L[1].rsrc,
-                    (int)((g & 1) ? kBig : q * 8u * E + 6u * (g >> 1) * 2u + soff(L[1], rp, 0)), 0, AUX_NT);
-            } else {
-                const i32x2 d = {__float_as_int(0.25f * s0), __float_as_int(0.25f * s1)};
-                __builtin_amdgcn_raw_buffer_store_b64(d, L[1].rsrc, (int)(q * 32u + 8u * g + soff(L[1], rp, 0)), 0,
-                                                      AUX_NT);
-            }
+            const i32x2 d = {__float_as_int(0.25f * s0), __float_as_int(0.25f * s1)};
+            __builtin_amdgcn_raw_buffer_store_b64(d, L[1].rsrc, (int)(q * 32u + 8u * g + soff(L[1], rp, 0)), 0, AUX_NT);
             const float t = s0 + s1;
             t2[rp >> 1] = (rp & 1) ? t2[rp >> 1] + t : t;
         }
         // level 2: lane g holds level-2 col g of rows 0 and 1
 #pragma unroll
-        for (int y2 = 0; y2 < 2; ++y2) {
-            if constexpr (S24) {
-                // lane g = 0 collects cols 0..3 (lanes + 16, + 32, + 48) and writes the 12-byte chunk
-                const int l = threadIdx.x & 63;
-                const float v = 0.0625f * t2[y2];
-                const float v1 = __shfl(v, (l + 16) & 63), v2 = __shfl(v, (l + 32) & 63), v3 = __shfl(v, (l + 48) & 63);
-                __builtin_amdgcn_raw_buffer_store_b96(pack24(v, v1, v2, v3), L[2].rsrc,
-                                                      (int)(g ? kBig : q * 4u * E + soff(L[2], y2, 0)), 0, AUX_NT);
-            } else {
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(0.0625f * t2[y2]), L[2].rsrc,
-                                                      (int)(q * 16u + 4u * g + soff(L[2], y2, 0)), 0, AUX_NT);
-            }
-        }
+        for (int y2 = 0; y2 < 2; ++y2)
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(0.0625f * t2[y2]), L[2].rsrc,
+                                                  (int)(q * 16u + 4u * g + soff(L[2], y2, 0)), 0, AUX_NT);
         // level 3: col x3 = level-2 cols 2 x3, 2 x3 + 1 (lanes g, g ^ 1 = lane ^ 16); even g hold col g >> 1
         float t3 = t2[0] + t2[1];
         t3 += __shfl_xor(t3, 16);
-        const float v3 = (1.0f / 64.0f) * t3;
-        if constexpr (S24) {
-            // lane g = 0 takes col 1 from lane + 32 and writes the block's 6-byte half of the 12-byte chunk as
-            // a naturally aligned word + short
-            const float w1 = __shfl_xor(v3, 32);
-            const unsigned r0 = s24_round(v3), r1 = s24_round(w1);
-            const unsigned base = q * 12u + soff(L[3], 0, 0);          // 1 x 4 chunks: 2-aligned half chunk
-            const bool odd = ((base + L[3].a) & 2u) != 0;
-            // even: word = bytes 0-3, short = bytes 4-5; odd: short = bytes 0-1, word = bytes 2-5
-            const unsigned word = odd ? __builtin_amdgcn_perm(r1, r0, 0x07060503u) : __builtin_amdgcn_perm(r1, r0, 0x05030201u);
-            const unsigned shrt = odd ? ((r0 >> 8) & 0xffffu) : (r1 >> 16);
-            __builtin_amdgcn_raw_buffer_store_b32((int)word, L[3].rsrc, (int)(g ? kBig : base + (odd ? 2u : 0u)), 0, AUX_NT);
-            __builtin_amdgcn_raw_buffer_store_b16((short)shrt, L[3].rsrc, (int)(g ? kBig : base + (odd ? 0u : 4u)), 0,
-                                                  AUX_NT);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(v3), L[3].rsrc,
-                                                  (int)((g & 1) ? kBig : q * 8u + 4u * (g >> 1) + soff(L[3], 0, 0)), 0,
-                                                  AUX_NT);
-        }
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_int((1.0f / 64.0f) * t3), L[3].rsrc,
+                                              (int)((g & 1) ? kBig : q * 8u + 4u * (g >> 1) + soff(L[3], 0, 0)), 0,
+                                              AUX_NT);
     }
 }
 
-// S24 epilogue (round 6).  The F32-style epilogue above spent ~875 VALU instructions per 32-query tile
-// (the NaN-safe rounding, per-store address arithmetic and ds_bpermute gathers) against the partner wave's
-// 384 MFMAs, whose issue gaps hold ~2 VALU each, so it stretched the MFMA phase and held the clock down
-// (profiles/x3_epi_r06.json).  This one computes the same values in the same order and stores the same
-// bytes with ~1/3 of the VALU and 23 instead of 32 stores:
+// S24 epilogue (round 6).  An S24 epilogue shaped like the F32 one above (in git history) spent ~875 VALU
+// instructions per 32-query tile (the NaN-safe rounding, per-store address arithmetic and ds_bpermute
+// gathers) against the partner wave's 384 MFMAs, whose issue gaps hold ~2 VALU each, so it stretched the
+// MFMA phase and held the clock down (profiles/x3_epi_r06.json).  This one computes the same values in
+// the same order and stores the same bytes with ~1/3 of the VALU and 23 instead of 32 stores:
 //  * every store's byte offset is a per-lane constant (S24Off, computed once per kernel) from a descriptor
 //    rebased by the tile's uniform qt * 32 * stride (SALU: rebase);
 //  * level 1: the two 16-query halves (u) go out in ONE store: lane row g holds level-1 cols 2g, 2g+1 of
@@ -478,10 +403,11 @@ __device__ __forceinline__ void epilogue16_s24(const f32x4 (&acc)[8][2], const L
     }
 }
 
-// One segment of a workgroup's work: target block tb of image b against query tiles [qlo, qhi).  Every
-// wave runs 2 ceil((qhi - qlo) / 8) + 1 barriers; after the last one no wave reads LDS any more, so the
-// next segment may restage A at once.
-template <int ABL, bool S24>
+// One workgroup's work: target block tb of image b against query tiles [qlo, qhi).  After the A block
+// is staged the waves run free: ping-pong phase barriers between the two waves of a SIMD cost more than
+// they hid once the S24 epilogue shrank (cfg2 0.464-0.466 vs 0.477-0.479 ms in the bench step, GRBM
+// cycles 6.89M vs 7.42M, MFMA busy 0.69 vs 0.64; profiles/x3_free_ab_r06.json).
+template <bool S24>
 __device__ __forceinline__ void x3_segment(const __bf16* __restrict__ aHi, const __bf16* __restrict__ aLo,
                                            const __bf16* __restrict__ bHi, const __bf16* __restrict__ bLo,
                                            const PyrGeom& g, unsigned char* __restrict__ pyr, unsigned char* smem,
@@ -542,7 +468,7 @@ __device__ __forceinline__ void x3_segment(const __bf16* __restrict__ aHi, const
         const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)bp);
         const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)bp >> 32));
         L[l].rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uintptr_t)hi32 << 32) | lo32), (short)0,
-                                                      (int)__builtin_amdgcn_readfirstlane(ABL == 1 ? 0u : (unsigned)rows * rs),
+                                                      (int)__builtin_amdgcn_readfirstlane((unsigned)rows * rs),
                                                       0x00020000);
         L[l].rs = __builtin_amdgcn_readfirstlane(rs);
         L[l].cs = __builtin_amdgcn_readfirstlane((unsigned)N * cw * E);
@@ -550,7 +476,7 @@ __device__ __forceinline__ void x3_segment(const __bf16* __restrict__ aHi, const
         L[l].chunks = __builtin_amdgcn_readfirstlane(lv ? max(0, min(nch, g.tx[l] - xc0)) : 0);
         L[l].a = lo32 & 3u;
         L[l].base = ((unsigned long long)hi32 << 32) | lo32;
-        L[l].range = __builtin_amdgcn_readfirstlane(ABL == 1 ? 0u : (unsigned)rows * rs);
+        L[l].range = __builtin_amdgcn_readfirstlane((unsigned)rows * rs);
     }
 
     S24Off so;
@@ -587,13 +513,10 @@ __device__ __forceinline__ void x3_segment(const __bf16* __restrict__ aHi, const
                 rl[s][uu] = *reinterpret_cast<const bf16x8*>(p + uu * 4096 + 512 * s + lo_off);
             }
     }
-    vmcnt_pad_n<S24 ? (RMD_X3_S24_R05 ? kEpiStores16 + 1 : kEpiStoresS24) : kEpiStores16>(pyr);
-    // free-running waves (RMD_X3_FREE), or ping-pong phases: waves w and w + 4 of each SIMD alternate MFMA
-    // and epilogue
+    vmcnt_pad_n<S24 ? kEpiStoresS24 : kEpiStores16>(pyr);
+    // wave w takes tiles qlo + w, qlo + w + 8, ...: nw of the workgroup's nmax rounds
     const int nmax = (qhi - qlo + WAVES - 1) / WAVES;
     const int nw = qt < qhi ? (qhi - qt + WAVES - 1) / WAVES : 0;
-    const bool late = w >= 4;
-    if (late && ABL < 3 && !RMD_X3_FREE) __builtin_amdgcn_s_barrier();
     for (int k = 0; k < nmax; ++k) {
         const int qn = qt + WAVES;
         if (k < nw) {
@@ -602,26 +525,17 @@ __device__ __forceinline__ void x3_segment(const __bf16* __restrict__ aHi, const
             read_a16<0, 0>(a0, smem, bhi, blo);
             ksteps16<0>(acc, a0, a1, rh, rl, smem, bhi, blo, bq + (size_t)qt * 8192, bq + (size_t)min(qn, nqt - 1) * 8192,
                         lo_off);
-            if (ABL < 3 && !RMD_X3_FREE) __builtin_amdgcn_s_barrier();
-            if constexpr (ABL >= 2) {
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt) asm volatile("" ::"v"(acc[mt][0]), "v"(acc[mt][1]));
-            } else if constexpr (S24 && !RMD_X3_S24_R05) {
+            if constexpr (S24) {
                 if (qt * 32 + 32 <= N)
                     epilogue16_s24<false>(acc, L, so, qt, N, n, gq);
                 else
                     epilogue16_s24<true>(acc, L, so, qt, N, n, gq);
             } else {
-                epilogue16<S24>(acc, L, qt, N, n, gq);
+                epilogue16(acc, L, qt, N, n, gq);
             }
-            if (ABL < 3 && !RMD_X3_FREE) __builtin_amdgcn_s_barrier();
-        } else if (ABL < 3 && !RMD_X3_FREE) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_s_barrier();
         }
         qt = qn;
     }
-    if (!late && ABL < 3 && !RMD_X3_FREE) __builtin_amdgcn_s_barrier();
 }
 
 // Balanced schedule (round 6).  At cfg2 the 448 (image, block) workgroups of one-CU size run 1.75
@@ -638,7 +552,7 @@ struct X3Sched {
     int parts;    // query-tile parts of each remaining block
 };
 
-template <int ABL = 0, bool S24 = false>
+template <bool S24>
 __global__ void __launch_bounds__(512, 1)
 corr_pyramid_x3s(const __bf16* __restrict__ aHi, const __bf16* __restrict__ aLo, const __bf16* __restrict__ bHi,
                  const __bf16* __restrict__ bLo, PyrGeom g, int units, X3Sched sc, unsigned char* __restrict__ pyr) {
@@ -667,7 +581,7 @@ corr_pyramid_x3s(const __bf16* __restrict__ aHi, const __bf16* __restrict__ aLo,
         b = x * sc.ipx + jb;
         tb = j - jb * nblk;
     }
-    x3_segment<ABL, S24>(aHi, aLo, bHi, bLo, g, pyr, smem, b, tb, q0, q1);
+    x3_segment<S24>(aHi, aLo, bHi, bLo, g, pyr, smem, b, tb, q0, q1);
 }
 
 }  // namespace
@@ -708,11 +622,6 @@ int prepare(const float* f1, const float* f2, int C, float scale, const rmd_pyra
     return check_launch("rmd_corr_prepare/x3");
 }
 
-// RMD_X3_BAL = 0 (A/B builds): always one workgroup per (image, block)
-#ifndef RMD_X3_BAL
-#define RMD_X3_BAL 1
-#endif
-
 // the balanced schedule when every XCD holds the same whole images and one workgroup per (image, block)
 // would leave a partial last round (X3Sched)
 X3Sched schedule(const rmd_pyramid_desc& d, int nblk, int& grid) {
@@ -727,7 +636,7 @@ X3Sched schedule(const rmd_pyramid_desc& d, int nblk, int& grid) {
         else
             cus = -1;
     }
-    if (!RMD_X3_BAL || cus <= 0 || cus % 8 != 0 || d.batch % 8 != 0) return sc;
+    if (cus <= 0 || cus % 8 != 0 || d.batch % 8 != 0) return sc;
     if (units <= cus || units % cus == 0) return sc;
     const int wpx = cus / 8, nbx = d.batch / 8 * nblk;
     const int full = nbx / wpx, rest = nbx - full * wpx;
@@ -753,7 +662,7 @@ int pyramid(const rmd_pyramid_desc& d, void* pyr, void* ws, hipStream_t st) {
     const int units = nblk * d.batch;
     int grid = units;
     const X3Sched sc = schedule(d, nblk, grid);
-    auto kern = d.storage == RMD_S24 ? corr_pyramid_x3s<RMD_X3_ABL, true> : corr_pyramid_x3s<RMD_X3_ABL, false>;
+    auto kern = d.storage == RMD_S24 ? corr_pyramid_x3s<true> : corr_pyramid_x3s<false>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds16);
     kern<<<grid, 512, kLds16, st>>>(aHi, aLo, bHi, bLo, make_geom(d), units, sc,
                                                           reinterpret_cast<unsigned char*>(pyr));

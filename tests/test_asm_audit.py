@@ -161,8 +161,9 @@ def test_dicl_backward_has_no_flat_atomics():
 
 
 def test_product_library_reads_no_environment():
-    """A/B knobs and ablations live in the diagnostic build only (`make diag` -> librmd_diag.so):
-    the product library imports no getenv and names no RMD_* variable."""
+    """The product library takes no run-time knob: it imports no getenv and names none of the RMD_*
+    environment variables of the round-2 diagnostic build (removed in round 3).  An A/B arm is a separate
+    -D build of one source (tools/build_variant.sh) loaded through RMD_LIBRARY."""
     lib = os.path.join(ROOT, "raft-meets-dicl_amd", "rmd", "librmd.so")
     if not os.path.exists(lib):
         pytest.skip("librmd.so not built")
