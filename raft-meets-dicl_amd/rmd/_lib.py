@@ -1,8 +1,9 @@
 """ctypes binding of librmd.so — the C ABI declared in include/rmd.h.
 
 This is the reference-side binding a maintainer of qzed/raft-meets-dicl would add:
-plain pointers, sizes and the current HIP stream.  There is no CPU fallback: if the library is
-missing, or a tensor is not on the GPU, the call raises.
+plain pointers, sizes and the current HIP stream.  Every kernel launch of the package goes through
+launch() below.  CPU tensors never come here: they dispatch to the operators' CPU kernels (rmd/cpu.py).
+A GPU tensor never falls back to those: if the library is missing, the call raises.
 """
 
 import ctypes
@@ -215,4 +216,27 @@ def describe_for(batch, height, width, levels, storage, channels, compute):
 
 
 def stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    """torch's current stream of torch.device `device` (the raw handle: no Stream object is built)."""
+    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(device.index))
+
+
+def launch(symbol, on, *args):
+    """Call the C launcher `symbol` with `args` and torch's current stream of tensor `on`'s device
+    appended, that device current for the call (switched only when it differs), and check the result.
+    Tensors are passed as their data pointers; None, ints, floats and ready-made ctypes values (arrays,
+    structs, byref) go through as they are.  Only enqueues: no allocation, synchronisation or read-back
+    (these calls are captured into HIP graphs)."""
+    fn = getattr(lib(), symbol)
+    cargs = [ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+    dev = on.device
+    if dev.index == torch.cuda.current_device():
+        rc = fn(*cargs, stream_ptr(dev))
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*cargs, stream_ptr(dev))    # taken inside the guard
+    check(rc, symbol)
+
+
+def workspace(name, on, *dims):
+    """Uninitialised byte workspace of rmd_<name>_workspace_bytes(*dims) on tensor `on`'s device."""
+    return on.new_empty(getattr(lib(), f"rmd_{name}_workspace_bytes")(*dims), dtype=torch.uint8)

@@ -23,8 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _ATTN_SCHEMAS, _HEAD_SCHEMAS, _LOSS_SCHEMAS, _METRIC_SCHEMAS, _SCHEMAS, _STORAGE,
-                      check_attn_args, check_head_args, check_loss_args, check_metric_args, pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
+from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_head_args, check_loss_args, check_metric_args,
+                      pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
 def _delta(r, device):
@@ -405,9 +405,6 @@ def sequence_loss_backward(grad_loss, flows, target, valid, masks, mask_index, w
     return out
 
 
-_LOSS_KERNELS = {"sequence_loss": sequence_loss, "sequence_loss_backward": sequence_loss_backward}
-assert sorted(_LOSS_KERNELS) == sorted(_LOSS_SCHEMAS), "every rmd loss operator needs a CPU kernel"
-
 # ---- flow metrics (metrics/epe.py:35-53, fl_all.py:29-44, aae.py:30-44, flow.py:32-36) ------------
 
 def metric_angle(estimate, target):
@@ -466,11 +463,6 @@ def flow_metrics(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
     return torch.stack(rows)
 
 
-_METRIC_KERNELS = {"flow_metrics": flow_metrics}
-assert sorted(_METRIC_KERNELS) == sorted(_METRIC_SCHEMAS), "every rmd metric operator needs a CPU kernel"
-for _name, _fn in _METRIC_KERNELS.items():
-    LIB.impl(_name, _fn, "CPU")         # not differentiable: library.py's Autograd kernel serves every device
-
 # ---- DICL flow head (impls/dicl.py:31-85, 194-195, 202) --------------------------------------------
 
 def flow_regression(cost):
@@ -516,9 +508,6 @@ def dicl_flow_head_backward(grad, cost, eps):
         return torch.autograd.grad(dicl_flow_head(c, None, eps), c, grad.float())[0]
 
 
-_HEAD_KERNELS = {"dicl_flow_head": dicl_flow_head, "dicl_flow_head_backward": dicl_flow_head_backward}
-assert sorted(_HEAD_KERNELS) == sorted(_HEAD_SCHEMAS), "every rmd head operator needs a CPU kernel"
-
 # ---- hidden-state upsampler: local cross-attention (common/hsup.py:71-92) --------------------------
 
 def _window_views(t, window, h, w):
@@ -556,22 +545,14 @@ def local_cross_attn_backward(grad, q, k, v, win_y, win_x):
         return torch.autograd.grad(local_cross_attn(*ins, win_y, win_x), ins, grad.float())
 
 
-_ATTN_KERNELS = {"local_cross_attn": local_cross_attn, "local_cross_attn_backward": local_cross_attn_backward}
-assert sorted(_ATTN_KERNELS) == sorted(_ATTN_SCHEMAS), "every rmd upsampler operator needs a CPU kernel"
+# ---- registration ------------------------------------------------------------------------------
+#
+# The CPU kernel of an operator is the function of its name in this module.
 
-_KERNELS = {
-    "corr_pyramid": corr_pyramid, "corr_lookup": corr_lookup,
-    "corr_otf_prepare": corr_otf_prepare, "corr_otf_lookup": corr_otf_lookup,
-    "dicl_stack": dicl_stack, "dicl_stack_backward": dicl_stack_backward,
-    "dicl_stack_int": dicl_stack_int, "dicl_stack_int_backward": dicl_stack_int_backward,
-    "dicl_stack_int_warped": dicl_stack_int_warped, "dicl_stack_int_warped_backward": dicl_stack_int_warped_backward,
-    "dap": dap, "dap_transpose": dap_transpose, "dap_weight_grad": dap_weight_grad,
-    "up8": up8, "up8_backward": up8_backward, "softargmax": softargmax, "softargmax_backward": softargmax_backward,
-    "warp_backwards": warp_backwards, "warp_backwards_backward": warp_backwards_backward,
-}
-assert sorted(_KERNELS) == sorted(_SCHEMAS), "every rmd operator needs a CPU kernel"
+_KERNELS = {name: globals().get(name) for name in _OPS}
+assert all(_KERNELS.values()), f"every rmd operator needs a CPU kernel: {[n for n, f in _KERNELS.items() if not f]}"
 
-for _name, _fn in (list(_KERNELS.items()) + list(_LOSS_KERNELS.items()) + list(_HEAD_KERNELS.items())
-                   + list(_ATTN_KERNELS.items())):
+for _name, _fn in _KERNELS.items():
     LIB.impl(_name, _fn, "CPU")
-    LIB.impl(_name, _fn, "AutogradCPU")
+    if _name != "flow_metrics":         # not differentiable: library.py's Autograd kernel serves every device
+        LIB.impl(_name, _fn, "AutogradCPU")

@@ -21,7 +21,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _ptr, _stream
 
 FLOW_INF = 1e10            # TorchAdapter.flow_inf (input.py:241-243)
 
@@ -129,24 +128,21 @@ class InputSpec:
         else:
             hp, wp, ph1, ph2, pw1, pw2, mode = h, w, 0, 0, 0, 0, 0
         outs = []
-        with torch.cuda.device(device):
-            for im in (i1, i2):
-                o = torch.empty((b, c, hp, wp), dtype=torch.float32, device=device)
-                _lib.check(_lib.lib().rmd_input_images(
-                    _ptr(im), b, h, w, c, float(self.clip[0]), float(self.clip[1]), float(self.range[0]),
-                    float(self.range[1]), hp, wp, ph1, pw1, mode, _ptr(o), _stream(o)), "rmd_input_images")
-                outs.append(o)
-            fo = vo = None
-            if flow is not None:
-                fl = _to_gpu(flow, torch.float32, device)
-                va = _to_gpu(valid, torch.uint8, device)
-                if tuple(fl.shape) != (b, h, w, 2) or tuple(va.shape) != (b, h, w):
-                    raise ValueError(f"flow/valid must be (B,H,W,2)/(B,H,W), got {tuple(fl.shape)} / {tuple(va.shape)}")
-                fo = torch.empty((b, 2, hp, wp), dtype=torch.float32, device=device)
-                vo = torch.empty((b, hp, wp), dtype=torch.uint8, device=device)
-                _lib.check(_lib.lib().rmd_input_flow(_ptr(fl), _ptr(va), b, h, w, hp, wp, ph1, pw1, float(FLOW_INF),
-                                                     _ptr(fo), _ptr(vo), _stream(fo)), "rmd_input_flow")
-                vo = vo.bool()
+        for im in (i1, i2):
+            o = im.new_empty((b, c, hp, wp))
+            _lib.launch("rmd_input_images", im, im, b, h, w, c, float(self.clip[0]), float(self.clip[1]),
+                        float(self.range[0]), float(self.range[1]), hp, wp, ph1, pw1, mode, o)
+            outs.append(o)
+        fo = vo = None
+        if flow is not None:
+            fl = _to_gpu(flow, torch.float32, device)
+            va = _to_gpu(valid, torch.uint8, device)
+            if tuple(fl.shape) != (b, h, w, 2) or tuple(va.shape) != (b, h, w):
+                raise ValueError(f"flow/valid must be (B,H,W,2)/(B,H,W), got {tuple(fl.shape)} / {tuple(va.shape)}")
+            fo = fl.new_empty((b, 2, hp, wp))
+            vo = va.new_empty((b, hp, wp))
+            _lib.launch("rmd_input_flow", fl, fl, va, b, h, w, hp, wp, ph1, pw1, float(FLOW_INF), fo, vo)
+            vo = vo.bool()
         # input.py:133-135 adds (ph1, ph2) / (pw1, pw2) to the original ((0, h), (0, w)) extents
         extents = ((ph1, h + ph2), (pw1, w + pw2))
         return outs[0], outs[1], fo, vo, extents

@@ -1,11 +1,14 @@
 """torch.library registration of the rmd operators: `torch.ops.rmd.*` over the C ABI of librmd.so.
 
-Every operator has a CUDA (HIP) kernel — the ctypes call into include/rmd.h on torch's current
-stream —, a fake (meta) implementation that only computes output shapes (torch.compile /
-torch.export / FakeTensor tracing), a CPU kernel for CPU tensors (rmd/cpu.py: the reference's ATen
-algorithm, registered for CPU and AutogradCPU — a dispatch by device, never a fallback for a GPU
-tensor), and, where the reference's module is trained through it, an autograd formula whose backward
-is again an rmd operator.  Schemas follow SURVEY.md §8(b):
+One table (_OPS: name -> family, schema) defines every operator.  Each has a HIP kernel (CUDA dispatch
+key, registered with @_hip: the device checks, then one _lib.launch of the C entry point on torch's
+current stream), a fake (meta) kernel that only computes output shapes (torch.compile / torch.export /
+FakeTensor tracing; where both allocate the same outputs they share the function that states the shapes),
+a CPU kernel for CPU tensors (rmd/cpu.py: the reference's ATen algorithm, registered for CPU and
+AutogradCPU — a dispatch by device, never a fallback for a GPU tensor), and, where the reference's
+module is trained through it, an autograd formula whose backward is again an rmd operator.  A new
+operator is one table entry here, its kernels, and one function of its name in rmd/cpu.py.  Schemas
+follow SURVEY.md §8(b):
 
   corr_pyramid(fmap1, fmap2, levels, compute, storage, scale) -> pyramid     raft.py:18-47
   corr_lookup(pyramid, coords, levels, radius, level_mask) -> corr           raft.py:49-95
@@ -17,11 +20,10 @@ is again an rmd operator.  Schemas follow SURVEY.md §8(b):
   up8(mask, flow, temperature), softargmax(cost, levels, radius, T)          raft.py:98-190, 319-331
   warp_backwards(img2, flow, eps) -> (est, mask)                             common/warp.py:5-33
   sequence_loss(flows[], target, valid, masks[], ...) -> (loss, counts)      raft.py:616-644, loss/mlseq.py:34-67,
-        (the loss operators, listed by loss_operators())                     raft_dicl_ctf_l3.py:430-473, dicl.py:436-472
+                                                                             raft_dicl_ctf_l3.py:430-473, dicl.py:436-472
+  flow_metrics(estimates[], target, valid, distances[], ...) -> stats        metrics/epe.py, fl_all.py, aae.py, flow.py
   dicl_flow_head(cost, flow_coarse?, eps) -> (B, 3, h, w) flow + entropy     impls/dicl.py:31-85, 194-195, 202
-        (the head operators, listed by head_operators())
   local_cross_attn(q, k, v, win_y, win_x) -> (B, cv, h, w)                   common/hsup.py:71-92
-        (the upsampler operators, listed by attn_operators())
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -36,48 +38,101 @@ import torch
 
 from . import _lib
 
-_ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-
 LIB = torch.library.Library("rmd", "DEF")
 
-_SCHEMAS = {
-    "corr_pyramid": "corr_pyramid(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) -> Tensor",
-    "corr_lookup": "corr_lookup(Tensor pyramid, Tensor coords, int levels, int radius, int level_mask) -> Tensor",
-    "corr_otf_prepare": "corr_otf_prepare(Tensor fmap1, Tensor fmap2, int levels, int compute, float scale) -> Tensor",
-    "corr_otf_lookup": ("corr_otf_lookup(Tensor workspace, Tensor coords, int channels, int levels, int compute, "
-                        "int radius, int level_mask) -> Tensor"),
-    "dicl_stack": ("dicl_stack(Tensor fmap1, Tensor fmap2, Tensor coords, int radius, int level, int norm_h, "
-                   "int norm_w, bool extra_delta) -> Tensor"),
-    "dicl_stack_backward": ("dicl_stack_backward(Tensor grad, Tensor coords, int channels, int level_h, int level_w, "
-                            "int radius, int level, int norm_h, int norm_w, bool extra_delta) -> (Tensor, Tensor)"),
-    "dicl_stack_int": "dicl_stack_int(Tensor fmap1, Tensor fmap2, int ru, int rv) -> Tensor",
-    "dicl_stack_int_backward": "dicl_stack_int_backward(Tensor grad, Tensor fmap2, int ru, int rv) -> (Tensor, Tensor)",
-    "dicl_stack_int_warped": "dicl_stack_int_warped(Tensor fmap1, Tensor fmap2, Tensor flow, int ru, int rv) -> Tensor",
-    "dicl_stack_int_warped_backward": ("dicl_stack_int_warped_backward(Tensor grad, Tensor fmap2, Tensor flow, int ru, "
-                                       "int rv) -> (Tensor, Tensor)"),
-    "dap": "dap(Tensor x, Tensor weight) -> Tensor",
-    "dap_transpose": "dap_transpose(Tensor grad, Tensor weight) -> Tensor",
-    "dap_weight_grad": "dap_weight_grad(Tensor grad, Tensor x, int disp) -> Tensor",
-    "up8": "up8(Tensor mask, Tensor flow, float temperature) -> Tensor",
-    "up8_backward": "up8_backward(Tensor grad, Tensor mask, Tensor flow, float temperature) -> (Tensor, Tensor)",
-    "softargmax": "softargmax(Tensor cost, int levels, int radius, float temperature) -> Tensor",
-    "softargmax_backward": ("softargmax_backward(Tensor grad, Tensor cost, int levels, int radius, float temperature) "
-                            "-> Tensor"),
-    "warp_backwards": "warp_backwards(Tensor img2, Tensor flow, float eps) -> (Tensor, Tensor)",
-    "warp_backwards_backward": "warp_backwards_backward(Tensor grad, Tensor flow, float eps) -> Tensor",
+# name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
+# set (operators()); "loss", "metric", "head" and "attn" are listed by loss_operators(),
+# metric_operators(), head_operators() and attn_operators().
+_OPS = {
+    "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
+                              "-> Tensor"),
+    "corr_lookup": ("model", "(Tensor pyramid, Tensor coords, int levels, int radius, int level_mask) -> Tensor"),
+    "corr_otf_prepare": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, float scale) -> Tensor"),
+    "corr_otf_lookup": ("model", "(Tensor workspace, Tensor coords, int channels, int levels, int compute, int radius, "
+                                 "int level_mask) -> Tensor"),
+    "dicl_stack": ("model", "(Tensor fmap1, Tensor fmap2, Tensor coords, int radius, int level, int norm_h, "
+                            "int norm_w, bool extra_delta) -> Tensor"),
+    "dicl_stack_backward": ("model", "(Tensor grad, Tensor coords, int channels, int level_h, int level_w, int radius, "
+                                     "int level, int norm_h, int norm_w, bool extra_delta) -> (Tensor, Tensor)"),
+    "dicl_stack_int": ("model", "(Tensor fmap1, Tensor fmap2, int ru, int rv) -> Tensor"),
+    "dicl_stack_int_backward": ("model", "(Tensor grad, Tensor fmap2, int ru, int rv) -> (Tensor, Tensor)"),
+    "dicl_stack_int_warped": ("model", "(Tensor fmap1, Tensor fmap2, Tensor flow, int ru, int rv) -> Tensor"),
+    "dicl_stack_int_warped_backward": ("model", "(Tensor grad, Tensor fmap2, Tensor flow, int ru, int rv) "
+                                                "-> (Tensor, Tensor)"),
+    "dap": ("model", "(Tensor x, Tensor weight) -> Tensor"),
+    "dap_transpose": ("model", "(Tensor grad, Tensor weight) -> Tensor"),
+    "dap_weight_grad": ("model", "(Tensor grad, Tensor x, int disp) -> Tensor"),
+    "up8": ("model", "(Tensor mask, Tensor flow, float temperature) -> Tensor"),
+    "up8_backward": ("model", "(Tensor grad, Tensor mask, Tensor flow, float temperature) -> (Tensor, Tensor)"),
+    "softargmax": ("model", "(Tensor cost, int levels, int radius, float temperature) -> Tensor"),
+    "softargmax_backward": ("model", "(Tensor grad, Tensor cost, int levels, int radius, float temperature) -> Tensor"),
+    "warp_backwards": ("model", "(Tensor img2, Tensor flow, float eps) -> (Tensor, Tensor)"),
+    "warp_backwards_backward": ("model", "(Tensor grad, Tensor flow, float eps) -> Tensor"),
+    "sequence_loss": ("loss", "(Tensor[] flows, Tensor target, Tensor valid, Tensor[] masks, int[] mask_index, "
+                              "float[] weights, int norm, bool include_invalid, bool skip_empty, float scale) "
+                              "-> (Tensor, Tensor)"),
+    "sequence_loss_backward": ("loss", "(Tensor grad_loss, Tensor[] flows, Tensor target, Tensor valid, "
+                                       "Tensor[] masks, int[] mask_index, float[] weights, Tensor counts, "
+                                       "bool[] needs_grad, int norm, bool include_invalid, float scale) -> Tensor[]"),
+    "flow_metrics": ("metric", "(Tensor[] estimates, Tensor target, Tensor valid, float[] distances, float fl_abs, "
+                               "float fl_rel, float mag_ord) -> Tensor"),
+    "dicl_flow_head": ("head", "(Tensor cost, Tensor? flow_coarse, float eps) -> Tensor"),
+    "dicl_flow_head_backward": ("head", "(Tensor grad, Tensor cost, float eps) -> Tensor"),
+    "local_cross_attn": ("attn", "(Tensor q, Tensor k, Tensor v, int win_y, int win_x) -> Tensor"),
+    "local_cross_attn_backward": ("attn", "(Tensor grad, Tensor q, Tensor k, Tensor v, int win_y, int win_x) "
+                                          "-> (Tensor, Tensor, Tensor)"),
 }
-for _s in _SCHEMAS.values():
-    LIB.define(_s)
+for _name, (_, _schema) in _OPS.items():
+    LIB.define(_name + _schema)
 
 
-def _cuda(name):
-    """The HIP kernel of an operator (CUDA dispatch key); its CPU kernel lives in rmd/cpu.py.  Every
-    tensor argument must be a GPU tensor (the dispatcher picks this kernel when any one is)."""
+def _family(family):
+    return sorted(name for name, (f, _) in _OPS.items() if f == family)
+
+
+def operators():
+    """Names of the registered torch.ops.rmd model operators (SURVEY.md §8(b))."""
+    return _family("model")
+
+
+def loss_operators():
+    """Names of the registered torch.ops.rmd loss operators."""
+    return _family("loss")
+
+
+def metric_operators():
+    """Names of the registered torch.ops.rmd metric operators."""
+    return _family("metric")
+
+
+def head_operators():
+    """Names of the registered torch.ops.rmd DICL flow-head operators."""
+    return _family("head")
+
+
+def attn_operators():
+    """Names of the registered torch.ops.rmd hidden-state upsampler (local cross-attention) operators."""
+    return _family("attn")
+
+
+def _hip(name):
+    """Register the HIP kernel of an operator (CUDA dispatch key); its CPU kernel lives in rmd/cpu.py.
+    The dispatcher picks this kernel when any one tensor argument is on a GPU, and the launch hands raw
+    pointers to one device's stream: so every tensor argument — members of Tensor[] and non-None
+    Tensor? arguments too — must be a GPU tensor, and all of them on the same device."""
     def deco(fn):
         def kernel(*args):
+            dev = None
             for a in args:
-                if isinstance(a, torch.Tensor) and a.device.type != "cuda":
-                    raise ValueError(f"rmd::{name}: all tensors must be on the GPU, got one on {a.device}")
+                for t in a if isinstance(a, (list, tuple)) else (a,):
+                    if not isinstance(t, torch.Tensor):
+                        continue
+                    if t.device.type != "cuda":
+                        raise ValueError(f"rmd::{name}: all tensors must be on the GPU, got one on {t.device}")
+                    if dev is None:
+                        dev = t.device
+                    elif t.device != dev:
+                        raise ValueError(f"{name}: tensors on different devices ({dev} / {t.device})")
             return fn(*args)
         LIB.impl(name, kernel, "CUDA")
         return fn
@@ -88,24 +143,6 @@ def _fake(name):
     return torch.library.register_fake(f"rmd::{name}")
 
 
-class _Dev:
-    """Run a launch with the tensor's device current (only switches when it differs)."""
-
-    def __init__(self, t):
-        self.dev = t.device
-        self.ctx = None
-
-    def __enter__(self):
-        if self.dev.index is not None and self.dev.index != torch.cuda.current_device():
-            self.ctx = torch.cuda.device(self.dev)
-            self.ctx.__enter__()
-        return _lib.stream_ptr(self.dev)
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-
-
 def _f32(t):
     """fp32, contiguous, detached (no aten.to call for fp32 inputs: an operator below autograd must
     not hand back its own input)."""
@@ -113,6 +150,12 @@ def _f32(t):
     if t.dtype != torch.float32:
         t = t.to(torch.float32)
     return t.contiguous()
+
+
+def _like(t, shape=None):
+    """Uninitialised fp32 output on t's device, shaped `shape` or like t.  t.new_empty serves real and
+    fake tensors alike, so a HIP kernel and its fake kernel allocate from the one statement of a shape."""
+    return t.new_empty(t.shape if shape is None else shape, dtype=torch.float32)
 
 
 _DESC = {}
@@ -184,10 +227,19 @@ def new_pyramid(like, d):
     return pyramid_view(like.new_empty((d.total_elements,), dtype=_STORAGE[d.storage]), d.layout)
 
 
+def pyramid_buffers(f1, levels, compute, storage):
+    """What a pyramid GEMM over fmaps shaped like f1 (B, C, H, W) writes into: (desc, uninitialised
+    pyramid, workspace) — d.storage is the GEMM's own (S24 falls back to F32 off the x3 GEMM)."""
+    b, c, h, w = f1.shape
+    d = describe_for(b, h, w, levels, storage, c, compute)
+    ws = _lib.workspace("corr_pyramid", f1, ctypes.byref(d), c, compute)
+    return d, new_pyramid(f1, d), ws
+
+
 def s24_encode(x):
     """float tensor -> RMD_S24 bytes (n, 3): the top 24 bits of each fp32 word, rounded half away from
     zero on the magnitude; NaN stays a quiet NaN (include/rmd.h RMD_S24, the x3 GEMM's epilogue)."""
-    u = x.detach().float().contiguous().reshape(-1).view(torch.int32)
+    u = _f32(x).reshape(-1).view(torch.int32)
     nan = (u & 0x7fffffff) > 0x7f800000
     r = torch.where(nan, u | 0x00400000, u + 0x80)
     return r.view(torch.uint8).view(-1, 4)[:, 1:4].contiguous()
@@ -207,19 +259,12 @@ def _check_fmaps(f1, f2):
         raise ValueError(f"fmap1/fmap2 must be equal (B,C,H,W) shapes, got {tuple(f1.shape)} / {tuple(f2.shape)}")
 
 
-@_cuda("corr_pyramid")
+@_hip("corr_pyramid")
 def _corr_pyramid(fmap1, fmap2, levels, compute, storage, scale):
     _check_fmaps(fmap1, fmap2)
     f1, f2 = _f32(fmap1), _f32(fmap2)
-    b, c, h, w = f1.shape
-    d = describe_for(b, h, w, levels, storage, c, compute)
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_corr_pyramid_workspace_bytes(ctypes.byref(d), c, compute), dtype=torch.uint8,
-                     device=f1.device)
-    data = new_pyramid(f1, d)                         # d.storage: S24 falls back to F32 off the x3 GEMM
-    with _Dev(f1) as st:
-        _lib.check(lib.rmd_corr_pyramid(_ptr(f1), _ptr(f2), c, float(scale), ctypes.byref(d), compute, _ptr(data),
-                                        _ptr(ws), st), "rmd_corr_pyramid")
+    d, data, ws = pyramid_buffers(f1, levels, compute, storage)
+    _lib.launch("rmd_corr_pyramid", f1, f1, f2, f1.shape[1], float(scale), ctypes.byref(d), compute, data, ws)
     return data
 
 
@@ -234,56 +279,41 @@ def _(fmap1, fmap2, levels, compute, storage, scale):
     return new_pyramid(fmap1, d)
 
 
-def _lookup_out(pyramid, coords, levels, radius):
+def _lookup_out(coords, levels, radius):
     b, _, h, w = coords.shape
-    return coords.new_empty((b, levels * (2 * radius + 1) ** 2, h, w), dtype=torch.float32)
+    return _like(coords, (b, levels * (2 * radius + 1) ** 2, h, w))
 
 
-def _check_device(name, *ts):
-    dev = ts[0].device
-    for t in ts[1:]:
-        if t.device != dev:
-            raise ValueError(f"{name}: tensors on different devices ({dev} / {t.device})")
-
-
-@_cuda("corr_lookup")
+@_hip("corr_lookup")
 def _corr_lookup(pyramid, coords, levels, radius, level_mask):
     b, two, h, w = coords.shape
     if pyramid.dtype not in _STORAGE_CODE or not pyramid.is_contiguous():
         raise ValueError(f"corr_lookup: pyramid must be a contiguous float32/float16/uint8 (S24) tensor, got "
                          f"{pyramid.dtype} {tuple(pyramid.shape)}")
-    layout = pyramid_layout(pyramid)
-    _check_device("corr_lookup", pyramid, coords)
-    d = describe(b, h, w, levels, pyramid_storage(pyramid), layout)
+    d = describe(b, h, w, levels, pyramid_storage(pyramid), pyramid_layout(pyramid))
     if two != 2 or pyramid_elements(pyramid) != d.total_elements:
         raise ValueError(f"corr_lookup: coords {tuple(coords.shape)} do not match the pyramid ({pyramid.numel()} elements)")
     co = _f32(coords)
-    out = _lookup_out(pyramid, co, levels, radius)
-    with _Dev(co) as st:
-        _lib.check(_lib.lib().rmd_corr_lookup(_ptr(pyramid), ctypes.byref(d), _ptr(co), radius, level_mask, _ptr(out),
-                                              st), "rmd_corr_lookup")
+    out = _lookup_out(co, levels, radius)
+    _lib.launch("rmd_corr_lookup", co, pyramid, ctypes.byref(d), co, radius, level_mask, out)
     return out
 
 
 @_fake("corr_lookup")
 def _(pyramid, coords, levels, radius, level_mask):
     pyramid_layout(pyramid)
-    return _lookup_out(pyramid, coords, levels, radius)
+    return _lookup_out(coords, levels, radius)
 
 
-@_cuda("corr_otf_prepare")
+@_hip("corr_otf_prepare")
 def _corr_otf_prepare(fmap1, fmap2, levels, compute, scale):
     _check_fmaps(fmap1, fmap2)
     f1, f2 = _f32(fmap1), _f32(fmap2)
     b, c, h, w = f1.shape
-    lib = _lib.lib()
-    nbytes = lib.rmd_corr_otf_workspace_bytes(b, c, h, w, levels, compute)
-    if nbytes == 0:
+    ws = _lib.workspace("corr_otf", f1, b, c, h, w, levels, compute)
+    if ws.numel() == 0:
         raise ValueError(f"otf: unsupported sizes {tuple(f1.shape)} with {levels} levels")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=f1.device)
-    with _Dev(f1) as st:
-        _lib.check(lib.rmd_corr_otf_prepare(_ptr(f1), _ptr(f2), b, c, h, w, levels, float(scale), compute, _ptr(ws), st),
-                   "rmd_corr_otf_prepare")
+    _lib.launch("rmd_corr_otf_prepare", f1, f1, f2, b, c, h, w, levels, float(scale), compute, ws)
     return ws
 
 
@@ -293,10 +323,10 @@ def _(fmap1, fmap2, levels, compute, scale):
     if fmap1.device.type == "cpu":                  # rmd/cpu.py: fmap1 * scale + pooled levels, float32
         n = b * c * (h * w + sum((h >> i) * (w >> i) for i in range(levels)))
         return fmap1.new_empty((n,), dtype=torch.float32)
-    return fmap1.new_empty((_lib.lib().rmd_corr_otf_workspace_bytes(b, c, h, w, levels, compute),), dtype=torch.uint8)
+    return _lib.workspace("corr_otf", fmap1, b, c, h, w, levels, compute)
 
 
-@_cuda("corr_otf_lookup")
+@_hip("corr_otf_lookup")
 def _corr_otf_lookup(workspace, coords, channels, levels, compute, radius, level_mask):
     b, two, h, w = coords.shape
     # the workspace must be the one corr_otf_prepare built for these sizes and this compute mode: its
@@ -307,65 +337,61 @@ def _corr_otf_lookup(workspace, coords, channels, levels, compute, radius, level
         raise ValueError(f"corr_otf_lookup: workspace ({workspace.dtype}, {workspace.numel()} B) does not match "
                          f"coords {tuple(coords.shape)}, channels={channels}, levels={levels}, compute={compute} "
                          f"({want} B expected)")
-    _check_device("corr_otf_lookup", workspace, coords)
     co = _f32(coords)
-    out = _lookup_out(workspace, co, levels, radius)
-    with _Dev(co) as st:
-        _lib.check(_lib.lib().rmd_corr_otf_lookup(_ptr(workspace), b, channels, h, w, levels, compute, _ptr(co), radius,
-                                                  level_mask, _ptr(out), st), "rmd_corr_otf_lookup")
+    out = _lookup_out(co, levels, radius)
+    _lib.launch("rmd_corr_otf_lookup", co, workspace, b, channels, h, w, levels, compute, co, radius, level_mask, out)
     return out
 
 
 @_fake("corr_otf_lookup")
 def _(workspace, coords, channels, levels, compute, radius, level_mask):
-    return _lookup_out(workspace, coords, levels, radius)
+    return _lookup_out(coords, levels, radius)
 
 
 # ---- DICL displacement stacks -------------------------------------------------------------------
 
-def _stack_shape(f1, radius, extra):
+def _stack_out(f1, radius, extra):
     b, c, h, w = f1.shape
     d = 2 * radius + 1
-    return (b, d, d, 2 * c + (2 if extra else 0), h, w)
+    return _like(f1, (b, d, d, 2 * c + (2 if extra else 0), h, w))
 
 
-@_cuda("dicl_stack")
+@_hip("dicl_stack")
 def _dicl_stack(fmap1, fmap2, coords, radius, level, norm_h, norm_w, extra_delta):
     f1, f2, co = _f32(fmap1), _f32(fmap2), _f32(coords)
     b, c, h, w = f1.shape
     hl, wl = f2.shape[-2:]
     if f2.shape[:2] != (b, c) or tuple(co.shape) != (b, 2, h, w):
         raise ValueError("dicl_stack: fmap2 must be (B,C,hl,wl) and coords (B,2,h,w) matching fmap1")
-    out = torch.empty(_stack_shape(f1, radius, extra_delta), dtype=torch.float32, device=f1.device)
-    with _Dev(f1) as st:
-        _lib.check(_lib.lib().rmd_dicl_stack(_ptr(f1), _ptr(f2), _ptr(co), b, c, h, w, hl, wl, radius, level, norm_h,
-                                             norm_w, int(extra_delta), _ptr(out), st), "rmd_dicl_stack")
+    out = _stack_out(f1, radius, extra_delta)
+    _lib.launch("rmd_dicl_stack", f1, f1, f2, co, b, c, h, w, hl, wl, radius, level, norm_h, norm_w,
+                int(extra_delta), out)
     return out
 
 
 @_fake("dicl_stack")
 def _(fmap1, fmap2, coords, radius, level, norm_h, norm_w, extra_delta):
-    return fmap1.new_empty(_stack_shape(fmap1, radius, extra_delta), dtype=torch.float32)
+    return _stack_out(fmap1, radius, extra_delta)
 
 
-@_cuda("dicl_stack_backward")
+def _stack_grads(coords, channels, level_h, level_w):
+    b, _, h, w = coords.shape
+    return _like(coords, (b, channels, h, w)), _like(coords, (b, channels, level_h, level_w))
+
+
+@_hip("dicl_stack_backward")
 def _dicl_stack_backward(grad, coords, channels, level_h, level_w, radius, level, norm_h, norm_w, extra_delta):
     g, co = _f32(grad), _f32(coords)
     b, _, h, w = co.shape
-    g1 = torch.empty((b, channels, h, w), dtype=torch.float32, device=g.device)
-    g2 = torch.empty((b, channels, level_h, level_w), dtype=torch.float32, device=g.device)
-    with _Dev(g) as st:
-        _lib.check(_lib.lib().rmd_dicl_stack_backward(_ptr(g), _ptr(co), b, channels, h, w, level_h, level_w, radius,
-                                                      level, norm_h, norm_w, int(extra_delta), _ptr(g1), _ptr(g2), st),
-                   "rmd_dicl_stack_backward")
+    g1, g2 = _stack_grads(co, channels, level_h, level_w)
+    _lib.launch("rmd_dicl_stack_backward", g, g, co, b, channels, h, w, level_h, level_w, radius, level, norm_h,
+                norm_w, int(extra_delta), g1, g2)
     return g1, g2
 
 
 @_fake("dicl_stack_backward")
 def _(grad, coords, channels, level_h, level_w, radius, level, norm_h, norm_w, extra_delta):
-    b, _, h, w = coords.shape
-    return (coords.new_empty((b, channels, h, w), dtype=torch.float32),
-            coords.new_empty((b, channels, level_h, level_w), dtype=torch.float32))
+    return _stack_grads(coords, channels, level_h, level_w)
 
 
 def _dicl_stack_setup(ctx, inputs, output):
@@ -384,48 +410,41 @@ def _dicl_stack_bwd(ctx, grad):
 torch.library.register_autograd("rmd::dicl_stack", _dicl_stack_bwd, setup_context=_dicl_stack_setup)
 
 
-def _int_shape(f1, ru, rv):
+def _int_out(f1, ru, rv):
     b, c, h, w = f1.shape
-    return (b, 2 * ru + 1, 2 * rv + 1, 2 * c, h, w)
+    return _like(f1, (b, 2 * ru + 1, 2 * rv + 1, 2 * c, h, w))
 
 
-@_cuda("dicl_stack_int")
+@_hip("dicl_stack_int")
 def _dicl_stack_int(fmap1, fmap2, ru, rv):
     f1, f2 = _f32(fmap1), _f32(fmap2)
     b, c, h, w = f1.shape
     if tuple(f2.shape) != (b, c, h, w):
         raise ValueError("dicl_stack_int: fmap1 and fmap2 must have equal (B,C,h,w) shapes")
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_dicl_stack_int_workspace_bytes(b, h, w), dtype=torch.uint8, device=f1.device)
-    out = torch.empty(_int_shape(f1, ru, rv), dtype=torch.float32, device=f1.device)
-    with _Dev(f1) as st:
-        _lib.check(lib.rmd_dicl_stack_int(_ptr(f1), _ptr(f2), b, c, h, w, ru, rv, _ptr(out), _ptr(ws), st),
-                   "rmd_dicl_stack_int")
+    ws = _lib.workspace("dicl_stack_int", f1, b, h, w)
+    out = _int_out(f1, ru, rv)
+    _lib.launch("rmd_dicl_stack_int", f1, f1, f2, b, c, h, w, ru, rv, out, ws)
     return out
 
 
 @_fake("dicl_stack_int")
 def _(fmap1, fmap2, ru, rv):
-    return fmap1.new_empty(_int_shape(fmap1, ru, rv), dtype=torch.float32)
+    return _int_out(fmap1, ru, rv)
 
 
-@_cuda("dicl_stack_int_backward")
+@_hip("dicl_stack_int_backward")
 def _dicl_stack_int_backward(grad, fmap2, ru, rv):
     g, f2 = _f32(grad), _f32(fmap2)
     b, c, h, w = f2.shape
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_dicl_stack_int_workspace_bytes(b, h, w), dtype=torch.uint8, device=g.device)
-    g1 = torch.empty((b, c, h, w), dtype=torch.float32, device=g.device)
-    g2 = torch.empty_like(g1)
-    with _Dev(g) as st:
-        _lib.check(lib.rmd_dicl_stack_int_backward(_ptr(g), _ptr(f2), b, c, h, w, ru, rv, _ptr(g1), _ptr(g2), _ptr(ws),
-                                                   st), "rmd_dicl_stack_int_backward")
+    ws = _lib.workspace("dicl_stack_int", g, b, h, w)
+    g1, g2 = _like(f2), _like(f2)
+    _lib.launch("rmd_dicl_stack_int_backward", g, g, f2, b, c, h, w, ru, rv, g1, g2, ws)
     return g1, g2
 
 
 @_fake("dicl_stack_int_backward")
 def _(grad, fmap2, ru, rv):
-    return fmap2.new_empty(fmap2.shape, dtype=torch.float32), fmap2.new_empty(fmap2.shape, dtype=torch.float32)
+    return _like(fmap2), _like(fmap2)
 
 
 def _int_setup(ctx, inputs, output):
@@ -443,43 +462,36 @@ def _int_bwd(ctx, grad):
 torch.library.register_autograd("rmd::dicl_stack_int", _int_bwd, setup_context=_int_setup)
 
 
-@_cuda("dicl_stack_int_warped")
+@_hip("dicl_stack_int_warped")
 def _dicl_stack_int_warped(fmap1, fmap2, flow, ru, rv):
     f1, f2, fl = _f32(fmap1), _f32(fmap2), _f32(flow)
     b, c, h, w = f1.shape
     if tuple(f2.shape) != (b, c, h, w) or tuple(fl.shape) != (b, 2, h, w):
         raise ValueError("dicl_stack_int_warped: need fmap1, fmap2 (B,C,h,w) and flow (B,2,h,w)")
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_dicl_stack_int_warped_workspace_bytes(b, c, h, w), dtype=torch.uint8, device=f1.device)
-    out = torch.empty(_int_shape(f1, ru, rv), dtype=torch.float32, device=f1.device)
-    with _Dev(f1) as st:
-        _lib.check(lib.rmd_dicl_stack_int_warped(_ptr(f1), _ptr(f2), _ptr(fl), b, c, h, w, ru, rv, _ptr(out), _ptr(ws),
-                                                 st), "rmd_dicl_stack_int_warped")
+    ws = _lib.workspace("dicl_stack_int_warped", f1, b, c, h, w)
+    out = _int_out(f1, ru, rv)
+    _lib.launch("rmd_dicl_stack_int_warped", f1, f1, f2, fl, b, c, h, w, ru, rv, out, ws)
     return out
 
 
 @_fake("dicl_stack_int_warped")
 def _(fmap1, fmap2, flow, ru, rv):
-    return fmap1.new_empty(_int_shape(fmap1, ru, rv), dtype=torch.float32)
+    return _int_out(fmap1, ru, rv)
 
 
-@_cuda("dicl_stack_int_warped_backward")
+@_hip("dicl_stack_int_warped_backward")
 def _dicl_stack_int_warped_backward(grad, fmap2, flow, ru, rv):
     g, f2, fl = _f32(grad), _f32(fmap2), _f32(flow)
     b, c, h, w = f2.shape
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_dicl_stack_int_warped_workspace_bytes(b, c, h, w), dtype=torch.uint8, device=g.device)
-    g1 = torch.empty((b, c, h, w), dtype=torch.float32, device=g.device)
-    g2 = torch.empty_like(g1)
-    with _Dev(g) as st:
-        _lib.check(lib.rmd_dicl_stack_int_warped_backward(_ptr(g), _ptr(f2), _ptr(fl), b, c, h, w, ru, rv, _ptr(g1),
-                                                          _ptr(g2), _ptr(ws), st), "rmd_dicl_stack_int_warped_backward")
+    ws = _lib.workspace("dicl_stack_int_warped", g, b, c, h, w)
+    g1, g2 = _like(f2), _like(f2)
+    _lib.launch("rmd_dicl_stack_int_warped_backward", g, g, f2, fl, b, c, h, w, ru, rv, g1, g2, ws)
     return g1, g2
 
 
 @_fake("dicl_stack_int_warped_backward")
 def _(grad, fmap2, flow, ru, rv):
-    return fmap2.new_empty(fmap2.shape, dtype=torch.float32), fmap2.new_empty(fmap2.shape, dtype=torch.float32)
+    return _like(fmap2), _like(fmap2)
 
 
 def _warped_setup(ctx, inputs, output):
@@ -499,39 +511,38 @@ torch.library.register_autograd("rmd::dicl_stack_int_warped", _warped_bwd, setup
 
 # ---- displacement-aware projection ---------------------------------------------------------------
 
-def _dap_launch(x, weight, transpose, name):
+def _dap_launch(x, weight, transpose):
     b, dd = x.shape[0], weight.shape[0]
     if x.numel() % (b * dd) or weight.numel() != dd * dd:
         raise ValueError(f"dap: x {tuple(x.shape)} does not hold {dd} displacement channels per batch")
     xc = _f32(x)
     wc = _f32(weight).reshape(dd, dd)
-    out = torch.empty_like(xc)
-    with _Dev(xc) as st:
-        _lib.check(_lib.lib().rmd_dap(_ptr(xc), _ptr(wc), b, dd, xc.numel() // (b * dd), transpose, _ptr(out), st), name)
+    out = _like(xc)
+    _lib.launch("rmd_dap", xc, xc, wc, b, dd, xc.numel() // (b * dd), transpose, out)
     return out
 
 
-@_cuda("dap")
+@_hip("dap")
 def _dap(x, weight):
-    return _dap_launch(x, weight, 0, "rmd_dap")
+    return _dap_launch(x, weight, 0)
 
 
 @_fake("dap")
 def _(x, weight):
-    return x.new_empty(x.shape, dtype=torch.float32)
+    return _like(x)
 
 
-@_cuda("dap_transpose")
+@_hip("dap_transpose")
 def _dap_transpose(grad, weight):
-    return _dap_launch(grad, weight, 1, "rmd_dap^T")
+    return _dap_launch(grad, weight, 1)
 
 
 @_fake("dap_transpose")
 def _(grad, weight):
-    return grad.new_empty(grad.shape, dtype=torch.float32)
+    return _like(grad)
 
 
-@_cuda("dap_weight_grad")
+@_hip("dap_weight_grad")
 def _dap_weight_grad(grad, x, disp):
     """dW = sum_b g_b x_b^T (rmd_dap_weight_grad: split-bf16 MFMA, deterministic split-K)."""
     b = x.shape[0]
@@ -539,18 +550,15 @@ def _dap_weight_grad(grad, x, disp):
         raise ValueError(f"dap_weight_grad: grad {tuple(grad.shape)} / x {tuple(x.shape)} with {disp} displacements")
     gc, xc = _f32(grad), _f32(x)
     n = xc.numel() // (b * disp)
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_dap_weight_grad_workspace_bytes(b, disp, n), dtype=torch.uint8, device=xc.device)
-    out = torch.empty((disp, disp), dtype=torch.float32, device=xc.device)
-    with _Dev(xc) as st:
-        _lib.check(lib.rmd_dap_weight_grad(_ptr(gc), _ptr(xc), b, disp, n, _ptr(out), _ptr(ws), st),
-                   "rmd_dap_weight_grad")
+    ws = _lib.workspace("dap_weight_grad", xc, b, disp, n)
+    out = _like(xc, (disp, disp))
+    _lib.launch("rmd_dap_weight_grad", xc, gc, xc, b, disp, n, out, ws)
     return out
 
 
 @_fake("dap_weight_grad")
 def _(grad, x, disp):
-    return x.new_empty((disp, disp), dtype=torch.float32)
+    return _like(x, (disp, disp))
 
 
 def _dap_setup(ctx, inputs, output):
@@ -573,41 +581,40 @@ torch.library.register_autograd("rmd::dap", _dap_bwd, setup_context=_dap_setup)
 
 # ---- flow heads ----------------------------------------------------------------------------------
 
-@_cuda("up8")
+def _up8_out(flow):
+    b, _, h, w = flow.shape
+    return _like(flow, (b, 2, 8 * h, 8 * w))
+
+
+@_hip("up8")
 def _up8(mask, flow, temperature):
     b, c, h, w = flow.shape
     if c != 2 or tuple(mask.shape) != (b, 576, h, w):
         raise ValueError(f"up8: need flow (B,2,h,w) and mask (B,576,h,w), got {tuple(flow.shape)}, {tuple(mask.shape)}")
     mc, fc = _f32(mask), _f32(flow)
-    out = torch.empty((b, 2, 8 * h, 8 * w), dtype=torch.float32, device=fc.device)
-    with _Dev(fc) as st:
-        _lib.check(_lib.lib().rmd_up8(_ptr(mc), _ptr(fc), b, h, w, float(temperature), _ptr(out), st), "rmd_up8")
+    out = _up8_out(fc)
+    _lib.launch("rmd_up8", fc, mc, fc, b, h, w, float(temperature), out)
     return out
 
 
 @_fake("up8")
 def _(mask, flow, temperature):
-    b, _, h, w = flow.shape
-    return flow.new_empty((b, 2, 8 * h, 8 * w), dtype=torch.float32)
+    return _up8_out(flow)
 
 
-@_cuda("up8_backward")
+@_hip("up8_backward")
 def _up8_backward(grad, mask, flow, temperature):
     g, mc, fc = _f32(grad), _f32(mask), _f32(flow)
     b, _, h, w = fc.shape
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_up8_workspace_bytes(b, h, w), dtype=torch.uint8, device=g.device)
-    gm = torch.empty_like(mc)
-    gf = torch.empty_like(fc)
-    with _Dev(g) as st:
-        _lib.check(lib.rmd_up8_backward(_ptr(mc), _ptr(fc), _ptr(g), b, h, w, float(temperature), _ptr(gm), _ptr(gf),
-                                        _ptr(ws), st), "rmd_up8_backward")
+    ws = _lib.workspace("up8", g, b, h, w)
+    gm, gf = _like(mc), _like(fc)
+    _lib.launch("rmd_up8_backward", g, mc, fc, g, b, h, w, float(temperature), gm, gf, ws)
     return gm, gf
 
 
 @_fake("up8_backward")
 def _(grad, mask, flow, temperature):
-    return mask.new_empty(mask.shape, dtype=torch.float32), flow.new_empty(flow.shape, dtype=torch.float32)
+    return _like(mask), _like(flow)
 
 
 def _up8_setup(ctx, inputs, output):
@@ -625,45 +632,40 @@ def _up8_bwd(ctx, grad):
 torch.library.register_autograd("rmd::up8", _up8_bwd, setup_context=_up8_setup)
 
 
-def _sam_shape(cost, levels):
-    b = cost.shape[0]
-    return (levels, b, 2) + tuple(cost.shape[2:])
+def _sam_out(cost, levels):
+    return _like(cost, (levels, cost.shape[0], 2) + tuple(cost.shape[2:]))
 
 
-@_cuda("softargmax")
+@_hip("softargmax")
 def _softargmax(cost, levels, radius, temperature):
     b, ctot = cost.shape[:2]
     n = cost[0, 0].numel()
     if ctot < levels * (2 * radius + 1) ** 2:
         raise ValueError(f"softargmax: {ctot} channels < {levels} levels x {(2 * radius + 1) ** 2} displacements")
     cc = _f32(cost)
-    flows = torch.empty(_sam_shape(cc, levels), dtype=torch.float32, device=cc.device)
-    with _Dev(cc) as st:
-        _lib.check(_lib.lib().rmd_softargmax(_ptr(cc), b, ctot, n, levels, radius, float(temperature), _ptr(flows), st),
-                   "rmd_softargmax")
+    flows = _sam_out(cc, levels)
+    _lib.launch("rmd_softargmax", cc, cc, b, ctot, n, levels, radius, float(temperature), flows)
     return flows
 
 
 @_fake("softargmax")
 def _(cost, levels, radius, temperature):
-    return cost.new_empty(_sam_shape(cost, levels), dtype=torch.float32)
+    return _sam_out(cost, levels)
 
 
-@_cuda("softargmax_backward")
+@_hip("softargmax_backward")
 def _softargmax_backward(grad, cost, levels, radius, temperature):
     cc, g = _f32(cost), _f32(grad)
     b, ctot = cc.shape[:2]
     n = cc[0, 0].numel()
     gc = torch.zeros_like(cc) if ctot > levels * (2 * radius + 1) ** 2 else torch.empty_like(cc)
-    with _Dev(g) as st:
-        _lib.check(_lib.lib().rmd_softargmax_backward(_ptr(cc), _ptr(g), b, ctot, n, levels, radius, float(temperature),
-                                                      _ptr(gc), st), "rmd_softargmax_backward")
+    _lib.launch("rmd_softargmax_backward", g, cc, g, b, ctot, n, levels, radius, float(temperature), gc)
     return gc
 
 
 @_fake("softargmax_backward")
 def _(grad, cost, levels, radius, temperature):
-    return cost.new_empty(cost.shape, dtype=torch.float32)
+    return _like(cost)
 
 
 def _sam_setup(ctx, inputs, output):
@@ -683,40 +685,36 @@ torch.library.register_autograd("rmd::softargmax", _sam_bwd, setup_context=_sam_
 
 # ---- backward warp -------------------------------------------------------------------------------
 
-@_cuda("warp_backwards")
+@_hip("warp_backwards")
 def _warp_backwards(img2, flow, eps):
     b, c, h, w = img2.shape
     if tuple(flow.shape) != (b, 2, h, w):
         raise ValueError(f"warp_backwards: flow {tuple(flow.shape)} must be (B, 2, h, w) for img2 {tuple(img2.shape)}")
     ic, fc = _f32(img2), _f32(flow)
-    out = torch.empty_like(ic)
-    mask = torch.empty((b, 1, h, w), dtype=torch.uint8, device=ic.device)
-    with _Dev(ic) as st:
-        _lib.check(_lib.lib().rmd_warp_backwards(_ptr(ic), _ptr(fc), b, c, h, w, float(eps), _ptr(out), _ptr(mask), st),
-                   "rmd_warp_backwards")
+    out = _like(ic)
+    mask = ic.new_empty((b, 1, h, w), dtype=torch.uint8)        # the kernel writes bytes; the fake says bool
+    _lib.launch("rmd_warp_backwards", ic, ic, fc, b, c, h, w, float(eps), out, mask)
     return out, mask.bool()
 
 
 @_fake("warp_backwards")
 def _(img2, flow, eps):
     b, c, h, w = img2.shape
-    return img2.new_empty(img2.shape, dtype=torch.float32), img2.new_empty((b, 1, h, w), dtype=torch.bool)
+    return _like(img2), img2.new_empty((b, 1, h, w), dtype=torch.bool)
 
 
-@_cuda("warp_backwards_backward")
+@_hip("warp_backwards_backward")
 def _warp_backwards_backward(grad, flow, eps):
     g, fc = _f32(grad), _f32(flow)
     b, c, h, w = g.shape
-    gi = torch.empty_like(g)
-    with _Dev(g) as st:
-        _lib.check(_lib.lib().rmd_warp_backwards_backward(_ptr(g), _ptr(fc), b, c, h, w, float(eps), _ptr(gi), st),
-                   "rmd_warp_backwards_backward")
+    gi = _like(g)
+    _lib.launch("rmd_warp_backwards_backward", g, g, fc, b, c, h, w, float(eps), gi)
     return gi
 
 
 @_fake("warp_backwards_backward")
 def _(grad, flow, eps):
-    return grad.new_empty(grad.shape, dtype=torch.float32)
+    return _like(grad)
 
 
 def _warp_setup(ctx, inputs, output):
@@ -737,21 +735,9 @@ torch.library.register_autograd("rmd::warp_backwards", _warp_bwd, setup_context=
 
 # ---- sequence losses -----------------------------------------------------------------------------
 #
-# The loss operators take tensor lists (one entry per prediction).  They are kept in a table of their
-# own: _SCHEMAS / operators() is the SURVEY.md §8(b) model-operator set, loss_operators() lists these.
-# `masks` holds the distinct per-prediction masks and mask_index[k] the entry prediction k uses (-1:
-# the shared `valid`).  The list-valued autograd formula lives in rmd.ops (_SequenceLossFn).
-
-_LOSS_SCHEMAS = {
-    "sequence_loss": ("sequence_loss(Tensor[] flows, Tensor target, Tensor valid, Tensor[] masks, int[] mask_index, "
-                      "float[] weights, int norm, bool include_invalid, bool skip_empty, float scale) "
-                      "-> (Tensor, Tensor)"),
-    "sequence_loss_backward": ("sequence_loss_backward(Tensor grad_loss, Tensor[] flows, Tensor target, Tensor valid, "
-                               "Tensor[] masks, int[] mask_index, float[] weights, Tensor counts, bool[] needs_grad, "
-                               "int norm, bool include_invalid, float scale) -> Tensor[]"),
-}
-for _s in _LOSS_SCHEMAS.values():
-    LIB.define(_s)
+# The loss operators take tensor lists (one entry per prediction).  `masks` holds the distinct
+# per-prediction masks and mask_index[k] the entry prediction k uses (-1: the shared `valid`).  The
+# list-valued autograd formula lives in rmd.ops (_SequenceLossFn).
 
 LOSS_NORMS = (_lib.RMD_LOSS_L1, _lib.RMD_LOSS_L2, _lib.RMD_LOSS_ABSMEAN, _lib.RMD_LOSS_ROBUST)
 
@@ -789,95 +775,73 @@ def check_loss_args(flows, target, valid, masks, mask_index, weights, norm):
             raise ValueError(f"sequence_loss: mask index {i} with {len(masks)} masks")
 
 
-def _all_gpu(name, *tensors):
-    for t in tensors:
-        if t.device.type != "cuda":
-            raise ValueError(f"rmd::{name}: all tensors must be on the GPU, got one on {t.device}")
-    _check_device(name, *tensors)
-
-
 def _loss_table(flows, masks, mask_index, weights, grads=None):
     table = (_lib.LossPrediction * len(flows))()
     for k, f in enumerate(flows):
         e = table[k]
         e.flow = f.data_ptr()
         e.mask = masks[mask_index[k]].data_ptr() if mask_index[k] >= 0 else None
-        e.grad = grads[k].data_ptr() if grads is not None and grads[k] is not None else None
+        e.grad = grads[k].data_ptr() if grads is not None and grads[k].numel() else None
         e.height, e.width = f.shape[2], f.shape[3]
         e.weight = float(weights[k])
     return table
 
 
+def _loss_out(target, n):
+    return target.new_empty((), dtype=torch.float32), target.new_empty((n,), dtype=torch.int64)
+
+
+@_hip("sequence_loss")
 def _sequence_loss(flows, target, valid, masks, mask_index, weights, norm, include_invalid, skip_empty, scale):
     check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
-    _all_gpu("sequence_loss", target, valid, *flows, *masks)
     fl, tg, va, ms = [_f32(f) for f in flows], _f32(target), _u8(valid), [_u8(m) for m in masks]
     b, _, h, w = tg.shape
-    lib = _lib.lib()
     n = len(fl)
-    ws = torch.empty(lib.rmd_sequence_loss_workspace_bytes(b, h, w, min(n, _lib.LOSS_MAX_PREDICTIONS)),
-                     dtype=torch.uint8, device=tg.device)
-    loss = torch.empty((), dtype=torch.float32, device=tg.device)
-    counts = torch.empty((n,), dtype=torch.int64, device=tg.device)
-    table = _loss_table(fl, ms, mask_index, weights)
-    with _Dev(tg) as st:
-        _lib.check(lib.rmd_sequence_loss(table, n, _ptr(tg), _ptr(va), b, h, w, norm, int(include_invalid),
-                                         int(skip_empty), float(scale), _ptr(loss), _ptr(counts), _ptr(ws), st),
-                   "rmd_sequence_loss")
+    ws = _lib.workspace("sequence_loss", tg, b, h, w, min(n, _lib.LOSS_MAX_PREDICTIONS))
+    loss, counts = _loss_out(tg, n)
+    _lib.launch("rmd_sequence_loss", tg, _loss_table(fl, ms, mask_index, weights), n, tg, va, b, h, w, norm,
+                int(include_invalid), int(skip_empty), float(scale), loss, counts, ws)
     return loss, counts
-
-
-LIB.impl("sequence_loss", _sequence_loss, "CUDA")
 
 
 @_fake("sequence_loss")
 def _(flows, target, valid, masks, mask_index, weights, norm, include_invalid, skip_empty, scale):
     check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
-    return (target.new_empty((), dtype=torch.float32), target.new_empty((len(flows),), dtype=torch.int64))
+    return _loss_out(target, len(flows))
 
 
+def _loss_grads(flows, needs_grad):
+    """One gradient per prediction; a prediction that needs none gets an empty tensor (and the kernel a
+    null pointer for it, _loss_table)."""
+    return [_like(f, f.shape if need else (0,)) for f, need in zip(flows, needs_grad)]
+
+
+@_hip("sequence_loss_backward")
 def _sequence_loss_backward(grad_loss, flows, target, valid, masks, mask_index, weights, counts, needs_grad, norm,
                             include_invalid, scale):
     check_loss_args(flows, target, valid, masks, mask_index, weights, norm)
-    _all_gpu("sequence_loss_backward", grad_loss, target, valid, counts, *flows, *masks)
     if len(needs_grad) != len(flows) or counts.dtype != torch.int64 or counts.numel() != len(flows):
         raise ValueError("sequence_loss_backward: needs_grad and counts (int64) must have one entry per prediction")
     fl, tg, va, ms = [_f32(f) for f in flows], _f32(target), _u8(valid), [_u8(m) for m in masks]
     g, cn = _f32(grad_loss).reshape(()), counts.contiguous()
     b, _, h, w = tg.shape
-    # a prediction that needs no gradient gets none: a null pointer to the kernel, an empty tensor here
-    grads = [torch.empty_like(f) if need else None for f, need in zip(fl, needs_grad)]
+    grads = _loss_grads(fl, needs_grad)
     if any(needs_grad):
-        table = _loss_table(fl, ms, mask_index, weights, grads)
-        with _Dev(tg) as st:
-            _lib.check(_lib.lib().rmd_sequence_loss_backward(table, len(fl), _ptr(tg), _ptr(va), b, h, w, norm,
-                                                             int(include_invalid), float(scale), _ptr(g), _ptr(cn),
-                                                             st), "rmd_sequence_loss_backward")
-    return [x if x is not None else tg.new_empty((0,)) for x in grads]
-
-
-LIB.impl("sequence_loss_backward", _sequence_loss_backward, "CUDA")
+        _lib.launch("rmd_sequence_loss_backward", tg, _loss_table(fl, ms, mask_index, weights, grads), len(fl), tg, va,
+                    b, h, w, norm, int(include_invalid), float(scale), g, cn)
+    return grads
 
 
 @_fake("sequence_loss_backward")
 def _(grad_loss, flows, target, valid, masks, mask_index, weights, counts, needs_grad, norm, include_invalid, scale):
-    return [f.new_empty(f.shape if need else (0,), dtype=torch.float32) for f, need in zip(flows, needs_grad)]
+    return _loss_grads(flows, needs_grad)
 
 
 # ---- flow metrics --------------------------------------------------------------------------------
 #
-# A third table: metric_operators().  The operator returns the raw statistics of include/rmd.h
-# (estimates, samples, RMD_METRICS_SLOTS) float64; rmd.ops.flow_metrics derives the metrics from them.
-# It is not differentiable: its Autograd kernel runs the backend kernel below autograd, so the
-# result never carries a graph.
-
-_METRIC_SCHEMAS = {
-    "flow_metrics": ("flow_metrics(Tensor[] estimates, Tensor target, Tensor valid, float[] distances, float fl_abs, "
-                     "float fl_rel, float mag_ord) -> Tensor"),
-}
-for _s in _METRIC_SCHEMAS.values():
-    LIB.define(_s)
-
+# The operator returns the raw statistics of include/rmd.h (estimates, samples, RMD_METRICS_SLOTS)
+# float64; rmd.ops.flow_metrics derives the metrics from them.  It is not differentiable: its Autograd
+# kernel runs the backend kernel below autograd, so the result never carries a graph.
 
 def check_metric_args(estimates, target, valid, distances, mag_ord):
     """Shape and argument checks shared by the GPU, CPU and fake kernels of flow_metrics."""
@@ -899,30 +863,29 @@ def check_metric_args(estimates, target, valid, distances, mag_ord):
             raise ValueError(f"flow_metrics: an estimate must be {tuple(target.shape)}, got {tuple(e.shape)}")
 
 
+def _metrics_out(estimates, target):
+    return target.new_empty((len(estimates), target.shape[0], _lib.METRICS_SLOTS), dtype=torch.float64)
+
+
+@_hip("flow_metrics")
 def _flow_metrics(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
     check_metric_args(estimates, target, valid, distances, mag_ord)
-    _all_gpu("flow_metrics", target, valid, *estimates)
     es, tg, va = [_f32(e) for e in estimates], _f32(target), _u8(valid)
     b, _, h, w = tg.shape
-    lib = _lib.lib()
     n, nd = len(es), len(distances)
-    ws = torch.empty(lib.rmd_flow_metrics_workspace_bytes(b, h, w, n), dtype=torch.uint8, device=tg.device)
-    stats = torch.empty((n, b, _lib.METRICS_SLOTS), dtype=torch.float64, device=tg.device)
+    ws = _lib.workspace("flow_metrics", tg, b, h, w, n)
+    stats = _metrics_out(es, tg)
     table = (ctypes.c_void_p * n)(*[e.data_ptr() for e in es])
     dist = (ctypes.c_float * max(nd, 1))(*[float(d) for d in distances])
-    with _Dev(tg) as st:
-        _lib.check(lib.rmd_flow_metrics(table, n, _ptr(tg), _ptr(va), b, h, w, dist, nd, float(fl_abs), float(fl_rel),
-                                        float(mag_ord), _ptr(stats), _ptr(ws), st), "rmd_flow_metrics")
+    _lib.launch("rmd_flow_metrics", tg, table, n, tg, va, b, h, w, dist, nd, float(fl_abs), float(fl_rel),
+                float(mag_ord), stats, ws)
     return stats
-
-
-LIB.impl("flow_metrics", _flow_metrics, "CUDA")
 
 
 @_fake("flow_metrics")
 def _(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
     check_metric_args(estimates, target, valid, distances, mag_ord)
-    return target.new_empty((len(estimates), target.shape[0], _lib.METRICS_SLOTS), dtype=torch.float64)
+    return _metrics_out(estimates, target)
 
 
 def _flow_metrics_below_autograd(estimates, target, valid, distances, fl_abs, fl_rel, mag_ord):
@@ -935,17 +898,10 @@ LIB.impl("flow_metrics", _flow_metrics_below_autograd, "Autograd")
 
 # ---- DICL flow head ------------------------------------------------------------------------------
 #
-# A fourth table: head_operators().  One operator serves FlowRegression, FlowEntropy and the coarse-flow
-# addition of a DICL level (impls/dicl.py:31-85, :195): out (B, 3, h, w) holds the flow in channels 0-1
-# and the normalised entropy in channel 2.  Its autograd formula recomputes the softmax from the cost
+# One operator serves FlowRegression, FlowEntropy and the coarse-flow addition of a DICL level
+# (impls/dicl.py:31-85, :195): out (B, 3, h, w) holds the flow in channels 0-1 and the normalised
+# entropy in channel 2.  Its autograd formula recomputes the softmax from the cost
 # (dicl_flow_head_backward); the gradient of flow_coarse is the first two channels of the upstream one.
-
-_HEAD_SCHEMAS = {
-    "dicl_flow_head": "dicl_flow_head(Tensor cost, Tensor? flow_coarse, float eps) -> Tensor",
-    "dicl_flow_head_backward": "dicl_flow_head_backward(Tensor grad, Tensor cost, float eps) -> Tensor",
-}
-for _s in _HEAD_SCHEMAS.values():
-    LIB.define(_s)
 
 HEAD_MAX_RANGE = 8
 
@@ -971,48 +927,42 @@ def check_head_args(cost, flow_coarse, eps, grad=None):
             raise ValueError(f"dicl_flow_head: {name} must be a floating-point tensor, got {t.dtype}")
 
 
+def _head_out(cost):
+    b, _, _, h, w = cost.shape
+    return _like(cost, (b, 3, h, w))
+
+
+@_hip("dicl_flow_head")
 def _dicl_flow_head(cost, flow_coarse, eps):
     check_head_args(cost, flow_coarse, eps)
-    _all_gpu("dicl_flow_head", *([cost] if flow_coarse is None else [cost, flow_coarse]))
     cc = _f32(cost)
     fc = None if flow_coarse is None else _f32(flow_coarse)
     b, du, dv, h, w = cc.shape
-    out = torch.empty((b, 3, h, w), dtype=torch.float32, device=cc.device)
-    with _Dev(cc) as st:
-        _lib.check(_lib.lib().rmd_dicl_flow_head(_ptr(cc), None if fc is None else _ptr(fc), b, du, dv, h * w,
-                                                 float(eps), _ptr(out), st), "rmd_dicl_flow_head")
+    out = _head_out(cc)
+    _lib.launch("rmd_dicl_flow_head", cc, cc, fc, b, du, dv, h * w, float(eps), out)
     return out
-
-
-LIB.impl("dicl_flow_head", _dicl_flow_head, "CUDA")
 
 
 @_fake("dicl_flow_head")
 def _(cost, flow_coarse, eps):
     check_head_args(cost, flow_coarse, eps)
-    b, _, _, h, w = cost.shape
-    return cost.new_empty((b, 3, h, w), dtype=torch.float32)
+    return _head_out(cost)
 
 
+@_hip("dicl_flow_head_backward")
 def _dicl_flow_head_backward(grad, cost, eps):
     check_head_args(cost, None, eps, grad)
-    _all_gpu("dicl_flow_head_backward", grad, cost)
     g, cc = _f32(grad), _f32(cost)
     b, du, dv, h, w = cc.shape
-    gc = torch.empty_like(cc)
-    with _Dev(cc) as st:
-        _lib.check(_lib.lib().rmd_dicl_flow_head_backward(_ptr(cc), _ptr(g), b, du, dv, h * w, float(eps), _ptr(gc),
-                                                          st), "rmd_dicl_flow_head_backward")
+    gc = _like(cc)
+    _lib.launch("rmd_dicl_flow_head_backward", cc, cc, g, b, du, dv, h * w, float(eps), gc)
     return gc
-
-
-LIB.impl("dicl_flow_head_backward", _dicl_flow_head_backward, "CUDA")
 
 
 @_fake("dicl_flow_head_backward")
 def _(grad, cost, eps):
     check_head_args(cost, None, eps, grad)
-    return cost.new_empty(cost.shape, dtype=torch.float32)
+    return _like(cost)
 
 
 def _head_setup(ctx, inputs, output):
@@ -1037,17 +987,9 @@ torch.library.register_autograd("rmd::dicl_flow_head", _head_bwd, setup_context=
 
 # ---- hidden-state upsampler: local cross-attention -----------------------------------------------
 #
-# A fifth table: attn_operators().  local_cross_attn is the attention of HUpCrossAttn.forward
-# (common/hsup.py:71-92) without the expanded K / V; its autograd formula is local_cross_attn_backward,
-# which recomputes the softmax from q, k and v (nothing else is saved).
-
-_ATTN_SCHEMAS = {
-    "local_cross_attn": "local_cross_attn(Tensor q, Tensor k, Tensor v, int win_y, int win_x) -> Tensor",
-    "local_cross_attn_backward": ("local_cross_attn_backward(Tensor grad, Tensor q, Tensor k, Tensor v, int win_y, "
-                                  "int win_x) -> (Tensor, Tensor, Tensor)"),
-}
-for _s in _ATTN_SCHEMAS.values():
-    LIB.define(_s)
+# local_cross_attn is the attention of HUpCrossAttn.forward (common/hsup.py:71-92) without the
+# expanded K / V; its autograd formula is local_cross_attn_backward, which recomputes the softmax from
+# q, k and v (nothing else is saved).
 
 ATTN_WINDOWS = (1, 3, 5)
 ATTN_MAX_FACTOR = 64
@@ -1079,51 +1021,44 @@ def check_attn_args(q, k, v, win_y, win_x, grad=None):
             raise ValueError(f"local_cross_attn: {name} must be a floating-point tensor, got {t.dtype}")
 
 
+def _attn_out(q, v):
+    return _like(q, (q.shape[0], v.shape[1], q.shape[2], q.shape[3]))
+
+
+@_hip("local_cross_attn")
 def _local_cross_attn(q, k, v, win_y, win_x):
     check_attn_args(q, k, v, win_y, win_x)
-    _all_gpu("local_cross_attn", q, k, v)
     qc, kc, vc = _f32(q), _f32(k), _f32(v)
     b, ck, h, w = qc.shape
     _, cv, h2, w2 = vc.shape
-    out = torch.empty((b, cv, h, w), dtype=torch.float32, device=qc.device)
-    with _Dev(qc) as st:
-        _lib.check(_lib.lib().rmd_local_cross_attn(_ptr(qc), _ptr(kc), _ptr(vc), b, ck, cv, h, w, h2, w2, win_y, win_x,
-                                                   _ptr(out), st), "rmd_local_cross_attn")
+    out = _attn_out(qc, vc)
+    _lib.launch("rmd_local_cross_attn", qc, qc, kc, vc, b, ck, cv, h, w, h2, w2, win_y, win_x, out)
     return out
-
-
-LIB.impl("local_cross_attn", _local_cross_attn, "CUDA")
 
 
 @_fake("local_cross_attn")
 def _(q, k, v, win_y, win_x):
     check_attn_args(q, k, v, win_y, win_x)
-    return q.new_empty((q.shape[0], v.shape[1], q.shape[2], q.shape[3]), dtype=torch.float32)
+    return _attn_out(q, v)
 
 
+@_hip("local_cross_attn_backward")
 def _local_cross_attn_backward(grad, q, k, v, win_y, win_x):
     check_attn_args(q, k, v, win_y, win_x, grad)
-    _all_gpu("local_cross_attn_backward", grad, q, k, v)
     g, qc, kc, vc = _f32(grad), _f32(q), _f32(k), _f32(v)
     b, ck, h, w = qc.shape
     _, cv, h2, w2 = vc.shape
-    gq, gk, gv = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
-    nbytes = _lib.lib().rmd_local_cross_attn_workspace_bytes(b, h, w, win_y, win_x)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=qc.device)
-    with _Dev(qc) as st:
-        _lib.check(_lib.lib().rmd_local_cross_attn_backward(_ptr(g), _ptr(qc), _ptr(kc), _ptr(vc), b, ck, cv, h, w, h2,
-                                                            w2, win_y, win_x, _ptr(gq), _ptr(gk), _ptr(gv), _ptr(ws),
-                                                            st), "rmd_local_cross_attn_backward")
+    gq, gk, gv = _like(qc), _like(kc), _like(vc)
+    ws = _lib.workspace("local_cross_attn", qc, b, h, w, win_y, win_x)
+    _lib.launch("rmd_local_cross_attn_backward", qc, g, qc, kc, vc, b, ck, cv, h, w, h2, w2, win_y, win_x, gq, gk, gv,
+                ws)
     return gq, gk, gv
-
-
-LIB.impl("local_cross_attn_backward", _local_cross_attn_backward, "CUDA")
 
 
 @_fake("local_cross_attn_backward")
 def _(grad, q, k, v, win_y, win_x):
     check_attn_args(q, k, v, win_y, win_x, grad)
-    return tuple(t.new_empty(t.shape, dtype=torch.float32) for t in (q, k, v))
+    return _like(q), _like(k), _like(v)
 
 
 def _attn_setup(ctx, inputs, output):
@@ -1141,28 +1076,3 @@ def _attn_bwd(ctx, grad):
 
 
 torch.library.register_autograd("rmd::local_cross_attn", _attn_bwd, setup_context=_attn_setup)
-
-
-def operators():
-    """Names of the registered torch.ops.rmd model operators (SURVEY.md §8(b))."""
-    return sorted(_SCHEMAS)
-
-
-def loss_operators():
-    """Names of the registered torch.ops.rmd loss operators."""
-    return sorted(_LOSS_SCHEMAS)
-
-
-def metric_operators():
-    """Names of the registered torch.ops.rmd metric operators."""
-    return sorted(_METRIC_SCHEMAS)
-
-
-def head_operators():
-    """Names of the registered torch.ops.rmd DICL flow-head operators."""
-    return sorted(_HEAD_SCHEMAS)
-
-
-def attn_operators():
-    """Names of the registered torch.ops.rmd hidden-state upsampler (local cross-attention) operators."""
-    return sorted(_ATTN_SCHEMAS)

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib, config, library
 from ._lib import RMD_BF16, RMD_BF16X3, RMD_F16, RMD_F32, RMD_S24
+from .library import _f32
 
 # precision modes: (GEMM compute type, pyramid storage type)
 PRECISIONS = {
@@ -53,10 +54,6 @@ def _same_device(*tensors):
             dev = t.device
         elif t.device != dev:
             raise ValueError(f"rmd: tensors on different devices ({dev} / {t.device})")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class Pyramid:
@@ -122,21 +119,13 @@ def corr_pyramid(fmap1, fmap2, levels=4, precision=None, events=None, scale=None
         d = library.describe(b, h, w, levels, library.pyramid_storage(data), library.pyramid_layout(data))
         return Pyramid(data, d, c, scale)
     _require_gpu(fmap1, fmap2)
-    d = library.describe_for(b, h, w, levels, storage, c, compute)
-    f1 = fmap1.detach().float().contiguous()
-    f2 = fmap2.detach().float().contiguous()
-    lib = _lib.lib()
-    ws = torch.empty(lib.rmd_corr_pyramid_workspace_bytes(ctypes.byref(d), c, compute), dtype=torch.uint8,
-                     device=f1.device)
-    data = library.new_pyramid(f1, d)
-    with torch.cuda.device(f1.device):
-        stream = _lib.stream_ptr(f1.device)
-        _lib.check(lib.rmd_corr_prepare(_ptr(f1), _ptr(f2), c, scale, ctypes.byref(d), compute, _ptr(ws), stream),
-                   "rmd_corr_prepare")
+    f1, f2 = _f32(fmap1), _f32(fmap2)
+    d, data, ws = library.pyramid_buffers(f1, levels, compute, storage)
+    with torch.cuda.device(f1.device):                  # the events record on this device's current stream
+        _lib.launch("rmd_corr_prepare", f1, f1, f2, c, scale, ctypes.byref(d), compute, ws)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.check(lib.rmd_corr_pyramid_prepared(c, scale, ctypes.byref(d), compute, _ptr(data), _ptr(ws), stream),
-                   "rmd_corr_pyramid_prepared")
+        _lib.launch("rmd_corr_pyramid_prepared", f1, c, scale, ctypes.byref(d), compute, data, ws)
         e1.record()
         events.append((e0, e1))
     return Pyramid(data, d, c, scale)
@@ -209,19 +198,14 @@ class _OtfPrepareFn(torch.autograd.Function):
         o = st.otf
         if not st.records:
             return torch.zeros_like(st.f1), torch.zeros_like(st.f2), None
-        lib = _lib.lib()
-        nbytes = lib.rmd_corr_otf_backward_workspace_bytes(o.b, o.c, o.h, o.w, o.levels, o.compute)
-        if nbytes == 0:
+        ws = _lib.workspace("corr_otf_backward", st.f1, o.b, o.c, o.h, o.w, o.levels, o.compute)
+        if ws.numel() == 0:
             raise ValueError(f"otf backward: unsupported sizes (C={o.c} must be <= 256)")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=st.f1.device)
         g1 = torch.empty_like(st.f1)
         g2 = torch.empty_like(st.f2)
         recs = (ctypes.c_void_p * len(st.records))(*[r.data_ptr() for r in st.records])
-        with torch.cuda.device(st.f1.device):
-            _lib.check(lib.rmd_corr_otf_backward(_ptr(st.f1), _ptr(st.f2), _ptr(o.ws), o.b, o.c, o.h, o.w, o.levels,
-                                                 float(st.scale), o.compute, st.radius, len(st.records), recs,
-                                                 _ptr(g1), _ptr(g2), _ptr(ws), _stream(st.f1)),
-                       "rmd_corr_otf_backward")
+        _lib.launch("rmd_corr_otf_backward", st.f1, st.f1, st.f2, o.ws, o.b, o.c, o.h, o.w, o.levels, float(st.scale),
+                    o.compute, st.radius, len(st.records), recs, g1, g2, ws)
         st.records = []
         return g1, g2, None
 
@@ -236,7 +220,7 @@ class _OtfLookupFn(torch.autograd.Function):
         ctx.state = state
         ctx.radius = radius
         ctx.mask = _mask_bits(mask_costs, state.otf.levels)
-        ctx.save_for_backward(coords.detach().float().contiguous())
+        ctx.save_for_backward(_f32(coords))
         return out
 
     @staticmethod
@@ -247,13 +231,10 @@ class _OtfLookupFn(torch.autograd.Function):
         if st.radius is not None and st.radius != ctx.radius:
             raise ValueError("otf backward: all lookups of one block must use the same radius")
         st.radius = ctx.radius
-        lib = _lib.lib()
-        rec = torch.empty(lib.rmd_corr_otf_record_bytes(o.b, o.h, o.w, o.levels, ctx.radius), dtype=torch.uint8,
-                          device=co.device)
-        g = gout.float().contiguous()
-        with torch.cuda.device(co.device):
-            _lib.check(lib.rmd_corr_otf_record(_ptr(g), _ptr(co), o.b, o.h, o.w, o.levels, ctx.radius, ctx.mask,
-                                               _ptr(rec), _stream(co)), "rmd_corr_otf_record")
+        nbytes = _lib.lib().rmd_corr_otf_record_bytes(o.b, o.h, o.w, o.levels, ctx.radius)
+        rec = co.new_empty(nbytes, dtype=torch.uint8)
+        g = _f32(gout)
+        _lib.launch("rmd_corr_otf_record", co, g, co, o.b, o.h, o.w, o.levels, ctx.radius, ctx.mask, rec)
         st.records.append(rec)
         return gout.new_zeros(()), None, None, None, None
 
@@ -262,7 +243,7 @@ def otf_block_autograd(fmap1, fmap2, levels, precision, scale=1.0):
     """On-the-fly operands + autograd token for a block whose feature maps require gradients."""
     _require_gpu(fmap1, fmap2)
     otf = otf_prepare(fmap1, fmap2, levels, precision, scale=scale)
-    st = _OtfState(otf, fmap1.detach().float().contiguous(), fmap2.detach().float().contiguous(), scale)
+    st = _OtfState(otf, _f32(fmap1), _f32(fmap2), scale)
     token = _OtfPrepareFn.apply(fmap1, fmap2, st)
     return otf, st, token
 
@@ -328,20 +309,17 @@ def _build_grad(st, bf16=False):
                         device=dev)
     i = 0
     acc0 = 1 if st.grad is not None else 0
-    with torch.cuda.device(dev):
-        stream = _stream(G)
-        while i < len(pend):
-            j = i
-            while j < len(pend) and pend[j][2] == pend[i][2]:
-                j += 1
-            grp = pend[i:j]
-            gouts = (ctypes.c_void_p * len(grp))(*[x[0].data_ptr() for x in grp])
-            cos = (ctypes.c_void_p * len(grp))(*[x[1].data_ptr() for x in grp])
-            masks = (ctypes.c_uint * len(grp))(*[x[3] for x in grp])
-            _lib.check(lib.rmd_corr_grad_build_ex(gouts, cos, masks, len(grp), ctypes.byref(d), grp[0][2],
-                                                  1 if i > 0 else acc0, 1 if bf16 else 0, _ptr(G), stream),
-                       "rmd_corr_grad_build")
-            i = j
+    while i < len(pend):
+        j = i
+        while j < len(pend) and pend[j][2] == pend[i][2]:
+            j += 1
+        grp = pend[i:j]
+        gouts = (ctypes.c_void_p * len(grp))(*[x[0].data_ptr() for x in grp])
+        cos = (ctypes.c_void_p * len(grp))(*[x[1].data_ptr() for x in grp])
+        masks = (ctypes.c_uint * len(grp))(*[x[3] for x in grp])
+        _lib.launch("rmd_corr_grad_build_ex", G, gouts, cos, masks, len(grp), ctypes.byref(d), grp[0][2],
+                    1 if i > 0 else acc0, 1 if bf16 else 0, G)
+        i = j
     return G
 
 
@@ -371,33 +349,25 @@ class _CorrPyramidFn(torch.autograd.Function):
         scale = st.pyr.scale
         pooled = torch.empty((b, c, t), dtype=torch.float32, device=f1.device)
         g2 = torch.empty_like(f2)
-        with torch.cuda.device(f1.device):
-            stream = _stream(f1)
-            _lib.check(lib.rmd_corr_pool_targets(_ptr(f2), b, c, h, w, levels, scale, _ptr(pooled), stream),
-                       "rmd_corr_pool_targets")
-            G = st.grad                 # (B, T'/8, N, 8): element (t', p) at ((t'/8) N + p) 8 + t' % 8
-            g1 = torch.empty((b, c, n), dtype=torch.float32, device=f1.device)
-            dpool = torch.empty((b, c, t), dtype=torch.float32, device=f1.device)
-            ws = torch.empty(max(lib.rmd_corr_grad_gemm_workspace_bytes(b, c, t, n),
-                                 lib.rmd_corr_grad_gemm_workspace_bytes(b, c, n, t), 1),
-                             dtype=torch.uint8, device=f1.device)
-            # grad_fmap1 = P G (K = T', layout 3: G blocked along k), dP = fmap1 G^T (K = N, layout 2: G
-            # blocked along n): MFMA GEMMs (corr_grad.hip) in the block's compute — split-bf16 (fp32
-            # accuracy) for the fp32 modes, one bf16 product for the bf16 modes
-            gc = RMD_BF16 if bf16_mode else RMD_BF16X3
-            if G.dtype == torch.bfloat16:
-                # bfloat16 G (bf16 modes): the same products as the fp32-G GEMM, half the bytes
-                _lib.check(lib.rmd_corr_grad_gemm_bf16g(_ptr(pooled), t, _ptr(G), n, b, c, t, n, 3, _ptr(g1),
-                                                        _ptr(ws), stream), "rmd_corr_grad_gemm_bf16g")
-                _lib.check(lib.rmd_corr_grad_gemm_bf16g(_ptr(f1), n, _ptr(G), n, b, c, n, t, 2, _ptr(dpool),
-                                                        _ptr(ws), stream), "rmd_corr_grad_gemm_bf16g")
-            else:
-                _lib.check(lib.rmd_corr_grad_gemm(_ptr(pooled), t, _ptr(G), n, b, c, t, n, 3, gc, _ptr(g1),
-                                                  _ptr(ws), stream), "rmd_corr_grad_gemm")
-                _lib.check(lib.rmd_corr_grad_gemm(_ptr(f1), n, _ptr(G), n, b, c, n, t, 2, gc, _ptr(dpool),
-                                                  _ptr(ws), stream), "rmd_corr_grad_gemm")
-            _lib.check(lib.rmd_corr_unpool_targets(_ptr(dpool), b, c, h, w, levels, scale, _ptr(g2), stream),
-                       "rmd_corr_unpool_targets")
+        _lib.launch("rmd_corr_pool_targets", f1, f2, b, c, h, w, levels, scale, pooled)
+        G = st.grad                 # (B, T'/8, N, 8): element (t', p) at ((t'/8) N + p) 8 + t' % 8
+        g1 = torch.empty((b, c, n), dtype=torch.float32, device=f1.device)
+        dpool = torch.empty((b, c, t), dtype=torch.float32, device=f1.device)
+        ws = torch.empty(max(lib.rmd_corr_grad_gemm_workspace_bytes(b, c, t, n),
+                             lib.rmd_corr_grad_gemm_workspace_bytes(b, c, n, t), 1),
+                         dtype=torch.uint8, device=f1.device)
+        # grad_fmap1 = P G (K = T', layout 3: G blocked along k), dP = fmap1 G^T (K = N, layout 2: G
+        # blocked along n): MFMA GEMMs (corr_grad.hip) in the block's compute — split-bf16 (fp32
+        # accuracy) for the fp32 modes, one bf16 product for the bf16 modes
+        gc = RMD_BF16 if bf16_mode else RMD_BF16X3
+        if G.dtype == torch.bfloat16:
+            # bfloat16 G (bf16 modes): the same products as the fp32-G GEMM, half the bytes
+            _lib.launch("rmd_corr_grad_gemm_bf16g", f1, pooled, t, G, n, b, c, t, n, 3, g1, ws)
+            _lib.launch("rmd_corr_grad_gemm_bf16g", f1, f1, n, G, n, b, c, n, t, 2, dpool, ws)
+        else:
+            _lib.launch("rmd_corr_grad_gemm", f1, pooled, t, G, n, b, c, t, n, 3, gc, g1, ws)
+            _lib.launch("rmd_corr_grad_gemm", f1, f1, n, G, n, b, c, n, t, 2, gc, dpool, ws)
+        _lib.launch("rmd_corr_unpool_targets", f1, dpool, b, c, h, w, levels, scale, g2)
         st.grad = None
         return g1.view(b, c, h, w), g2, None
 
@@ -411,14 +381,14 @@ class _CorrLookupFn(torch.autograd.Function):
         ctx.state = state
         ctx.radius = radius
         ctx.mask = _mask_bits(mask_costs, state.pyr.levels)
-        ctx.save_for_backward(coords.detach().float().contiguous())
+        ctx.save_for_backward(_f32(coords))
         return out
 
     @staticmethod
     def backward(ctx, gout):
         (co,) = ctx.saved_tensors
         st = ctx.state
-        g = gout.float().contiguous()
+        g = _f32(gout)
         if GRAD_BUILD:
             # G is written from every lookup's gradient at once by the pyramid backward
             st.pending.append((g, co, ctx.radius, ctx.mask))
@@ -430,14 +400,8 @@ class _CorrLookupFn(torch.autograd.Function):
         if st.grad is None:
             t = lib.rmd_corr_grad_targets(d.height, d.width, d.levels)
             st.grad = torch.zeros(d.batch * d.height * d.width * t, dtype=torch.float32, device=co.device)
-        with torch.cuda.device(co.device):
-            _lib.check(lib.rmd_corr_lookup_backward(_ptr(g), ctx_desc(st), _ptr(co), ctx.radius, ctx.mask,
-                                                    _ptr(st.grad), _stream(co)), "rmd_corr_lookup_backward")
+        _lib.launch("rmd_corr_lookup_backward", co, g, ctypes.byref(d), co, ctx.radius, ctx.mask, st.grad)
         return gout.new_zeros(()), None, None, None, None
-
-
-def ctx_desc(st):
-    return ctypes.byref(st.pyr.desc)
 
 
 def corr_block_autograd(fmap1, fmap2, levels, precision, scale=None):
@@ -445,7 +409,7 @@ def corr_block_autograd(fmap1, fmap2, levels, precision, scale=None):
     _require_gpu(fmap1, fmap2)
     precision = precision or get_default_precision()
     pyr = corr_pyramid(fmap1, fmap2, levels, precision, scale=scale)
-    st = _CorrState(pyr, fmap1.detach().float().contiguous(), fmap2.detach().float().contiguous(), precision)
+    st = _CorrState(pyr, _f32(fmap1), _f32(fmap2), precision)
     token = _CorrPyramidFn.apply(fmap1, fmap2, st)
     return pyr, st, token
 
@@ -455,10 +419,6 @@ def corr_lookup_autograd(token, state, coords, radius, mask_costs=()):
 
 
 # ---- DICL cost volumes and DAP ------------------------------------------------------------------
-
-def _stream(t):
-    return _lib.stream_ptr(t.device)
-
 
 def dicl_stack(fmap1, fmap2, coords, radius, level=0, norm_hw=None, extra_delta=False):
     """(B,C,h,w), (B,C,hl,wl), (B,2,h,w) -> (B, 2r+1, 2r+1, 2C[+2], h, w) MatchingNet input
@@ -667,14 +627,6 @@ class FlowMetricsResult:
                                  packed[n:].view(extra.shape))
 
 
-def _widen(t):
-    """fp16 / bf16 (anything but fp32) widened, contiguous, detached."""
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 def flow_metrics(estimates, target, valid, distances=(1, 3, 5), fl=(3, 0.05), ord=2, extra=None):
     """The flow metrics of src/metrics (epe.py, fl_all.py, aae.py, flow.py) for every estimate and every
     sample in one fused pass (torch.ops.rmd.flow_metrics) -> FlowMetricsResult.  estimates: one tensor or
@@ -696,7 +648,7 @@ def flow_metrics(estimates, target, valid, distances=(1, 3, 5), fl=(3, 0.05), or
     if not ord > 0:
         raise ValueError(f"flow_metrics: bad ord {ord} (1, 2, inf or any other p > 0)")
     distances = [float(d) for d in distances]
-    es, tg, va = [_widen(e) for e in estimates], _widen(target), valid.detach().contiguous()
+    es, tg, va = [_f32(e) for e in estimates], _f32(target), valid.detach().contiguous()
     dstep, estep = _lib.METRICS_MAX_DISTANCES, _lib.METRICS_MAX_ESTIMATES
     rows = []
     for i in range(0, len(es), estep):

@@ -1,9 +1,10 @@
 """torch.library registration of the rmd operators (SURVEY.md §8(b) op schemas).
 
-CPU: every operator is registered with a schema, its fake (meta) kernel propagates shapes and dtypes
-without a GPU (FakeTensor tracing for torch.compile / export), and real CPU tensors raise (no CPU
-fallback).  GPU (marked): torch.library.opcheck — schema, fake-vs-real outputs, autograd
-registration — on small shapes of every operator family.
+CPU: every operator is registered with a schema and a kernel for every dispatch key it serves, its
+fake (meta) kernel propagates shapes and dtypes without a GPU (FakeTensor tracing for torch.compile /
+export), and real CPU tensors dispatch to the CPU kernels of rmd/cpu.py.  GPU (marked):
+torch.library.opcheck — schema, fake-vs-real outputs, autograd registration — on small shapes of
+every operator family, and the HIP kernels' rejection of a tensor argument left on the CPU.
 """
 
 import pytest
@@ -16,11 +17,26 @@ EXPECTED = ["corr_lookup", "corr_otf_lookup", "corr_otf_prepare", "corr_pyramid"
             "warp_backwards", "warp_backwards_backward"]
 
 
+FAMILIES = {"loss_operators": ["sequence_loss", "sequence_loss_backward"], "metric_operators": ["flow_metrics"],
+            "head_operators": ["dicl_flow_head", "dicl_flow_head_backward"],
+            "attn_operators": ["local_cross_attn", "local_cross_attn_backward"]}
+
+
 def test_every_operator_registered():
+    """All 26 operators of the five families exist and have a kernel for every dispatch key they serve:
+    HIP (CUDA), CPU, fake (Meta) and AutogradCPU — flow_metrics, which is not differentiable, has one
+    Autograd kernel for every device instead."""
     from rmd import library
     assert library.operators() == EXPECTED
-    for name in EXPECTED:
+    for family, names in FAMILIES.items():
+        assert getattr(library, family)() == names
+    every = EXPECTED + sum(FAMILIES.values(), [])
+    assert len(every) == len(set(every)) == 26
+    has = torch._C._dispatch_has_kernel_for_dispatch_key
+    for name in every:
         assert hasattr(torch.ops.rmd, name)
+        for key in ("CUDA", "CPU", "Meta", "Autograd" if name == "flow_metrics" else "AutogradCPU"):
+            assert has("rmd::" + name, key), f"rmd::{name} has no {key} kernel"
 
 
 def test_fake_kernels_propagate_shapes():
@@ -92,6 +108,28 @@ def test_opcheck_operator_families():
         pyr = torch.ops.rmd.corr_pyramid(f1.detach(), f2.detach(), 3, compute, storage, 0.25)
         torch.library.opcheck(torch.ops.rmd.corr_lookup, (pyr, co, 3, 2, 0),
                               test_utils=("test_schema", "test_autograd_registration", "test_faketensor"))
+
+
+@pytest.mark.gpu
+def test_hip_kernels_reject_a_cpu_tensor_argument():
+    """One operator per family called through torch.ops.rmd with valid tiny shapes and exactly one tensor
+    argument left on the CPU — a plain tensor, a member of a tensor list, the optional flow_coarse: the
+    HIP kernel raises before anything is launched."""
+    gpu = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device="cuda")  # noqa: E731
+    cpu = lambda *s: torch.zeros(*s)  # noqa: E731
+    target, valid = gpu(1, 2, 4, 5), gpu(1, 4, 5, dtype=torch.bool)
+    ops = torch.ops.rmd
+    cases = [
+        (ops.dicl_stack, (gpu(1, 8, 4, 5), gpu(1, 8, 4, 5), cpu(1, 2, 4, 5), 1, 0, 4, 5, False)),       # plain
+        (ops.local_cross_attn, (gpu(1, 4, 4, 4), cpu(1, 4, 2, 2), gpu(1, 4, 2, 2), 3, 3)),              # plain
+        (ops.sequence_loss, ([gpu(1, 2, 4, 5), cpu(1, 2, 4, 5)], target, valid, [], [-1, -1], [1.0, 0.5], 1,
+                             False, False, 1.0)),                                                       # list member
+        (ops.flow_metrics, ([cpu(1, 2, 4, 5), gpu(1, 2, 4, 5)], target, valid, [1.0], 3.0, 0.05, 2.0)), # list member
+        (ops.dicl_flow_head, (gpu(1, 3, 3, 4, 5), cpu(1, 2, 4, 5), 1e-9)),                              # Tensor?
+    ]
+    for op, args in cases:
+        with pytest.raises(ValueError, match="must be on the GPU"):
+            op(*args)
 
 
 @pytest.mark.parametrize("kind,fixture", [("dicl", "dicl_b1_c16_8x12"), ("dicl-1x1", "dicl1x1_b2_c16_8x12"),
