@@ -619,6 +619,37 @@ int rmd_flow_metrics(const float* const* estimates, int nest, const float* targe
                      int batch, int height, int width, const float* distances, int nd, float fl_abs, float fl_rel,
                      float mag_ord, double* stats, void* workspace, void* stream);
 
+/*
+ * Fused dicl-1x1 cost: the displacement gather of corr.dicl_1x1.CorrelationModule.forward
+ * (src/models/common/corr/dicl_1x1.py:51-79) and MatchingNet1x1 (dicl_1x1.py:8-30) with its norm layers
+ * folded into the weights, in one kernel; neither the (B, d, d, 2C, h, w) stack nor a hidden activation
+ * is written.  fmap1, fmap2 (B, C, h, w), coords (B, 2, h, w), out (B, 2r+1, 2r+1, h, w) (dim 1 = x offset,
+ * dim 2 = y offset), all float32.  For pixel p and displacement (a, bb) the column is
+ *   x = [fmap1[:, p] ; bilinear(fmap2, coords[p] + (a - r, bb - r))]
+ * sampled as rmd_dicl_stack does at level 0 with fmap1's own (h, w) (zero padding per tap; a non-finite
+ * sample position gives NaN samples), and
+ *   out = w4 . relu(W3 relu(W2 relu(W1 x + t1) + t2) + t3) + b4
+ * with W1 (c1, 2C), W2 (c2, c1), W3 (c3, c2) row-major, t1..t3 and w4 (c3) vectors, b4 one float, all
+ * float32 device memory; relu keeps NaN as torch's does.  C a multiple of 16 up to 64; c1, c2, c3
+ * multiples of 32 up to 128 (a caller pads narrower layers with zero rows / columns: relu(0) = 0 adds
+ * nothing); radius 1..4 — rmd_dicl_match_1x1_supported answers 1 for exactly these (host only), and
+ * every other call fails with RMD_ERR_SHAPE.
+ *   compute = RMD_BF16X3 : three split-bf16 MFMA products per layer (hi.hi + hi.lo + lo.hi), fp32
+ *                          accumulation — the parity mode
+ *   compute = RMD_BF16   : one bf16 product per layer
+ * The last layer and the biases are fp32 in both.  Hidden activations pass through bfloat16 (hi + lo in
+ * the parity mode), so an activation beyond bfloat16's range turns non-finite.  `workspace` holds
+ * rmd_dicl_match_1x1_workspace_bytes() bytes (0 = unsupported arguments): the call first repacks the
+ * weights into it as MFMA A fragments, so it may be reused by the next call on the same stream.
+ * Every output is computed from its own column only, in a fixed order: bitwise reproducible.
+ */
+int rmd_dicl_match_1x1_supported(int channels, int c1, int c2, int c3, int radius);
+size_t rmd_dicl_match_1x1_workspace_bytes(int channels, int c1, int c2, int c3, int compute);
+int rmd_dicl_match_1x1(const float* fmap1, const float* fmap2, const float* coords, int batch, int channels,
+                       int height, int width, int radius, const float* w1, const float* t1, const float* w2,
+                       const float* t2, const float* w3, const float* t3, const float* w4, const float* b4,
+                       int c1, int c2, int c3, int compute, float* out, void* workspace, void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

@@ -115,6 +115,9 @@ _SIGS = {
     "rmd_softargmax_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_dicl_flow_head": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
     "rmd_dicl_flow_head_backward": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P]),
+    "rmd_dicl_match_1x1_supported": (_I, [_I] * 5),
+    "rmd_dicl_match_1x1_workspace_bytes": (ctypes.c_size_t, [_I] * 5),
+    "rmd_dicl_match_1x1": (_I, [_P, _P, _P] + [_I] * 5 + [_P] * 8 + [_I] * 4 + [_P, _P, _P]),
     "rmd_local_cross_attn_kernel": (ctypes.c_char_p, [_I] * 9),
     "rmd_local_cross_attn": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P]),
     "rmd_local_cross_attn_workspace_bytes": (ctypes.c_size_t, [_I] * 5),

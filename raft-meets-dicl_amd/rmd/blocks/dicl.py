@@ -2,8 +2,10 @@
 
 MatchingNet stays a plain nn.Sequential of MIOpen convolutions (out of scope for custom kernels)
 with the reference's module names, so checkpoints load unchanged (`mnet.0.0.weight`, ...) and
-forward hooks on `*.mnet` keep working.  DisplacementAwareProjection keeps its `conv1` parameter
-((D, D, 1, 1), identity init) but runs the projection through rmd_dap.
+forward hooks on `*.mnet` keep working.  MatchingNet1x1 is the same, and given an ops.StackSpec
+instead of the stack it returns the fused rmd_dicl_match_1x1 cost of its folded parameters.
+DisplacementAwareProjection keeps its `conv1` parameter ((D, D, 1, 1), identity init) but runs the
+projection through rmd_dap.
 """
 
 import numpy as np
@@ -78,7 +80,51 @@ class MatchingNet1x1(nn.Sequential):
             nn.Conv2d(c3, 1, kernel_size=1),
         )
 
+    @staticmethod
+    def _norm_foldable(norm):
+        """Eval-mode batch norm with running statistics, or no norm at all: a per-channel affine map that
+        does not depend on the input.  Group, instance and train-mode batch norm need per-call statistics."""
+        if isinstance(norm, nn.BatchNorm2d):
+            return not norm.training and norm.track_running_stats and norm.running_mean is not None
+        return isinstance(norm, nn.Sequential) and len(norm) == 0
+
+    def foldable(self):
+        """Whether folded() can state every ConvBlock as relu(W' x + t)."""
+        return all(self._norm_foldable(block[1]) for block in list(self)[:3])
+
+    def folded(self):
+        """([W1', W2', W3', w4], [t1, t2, t3, b4]): each ConvBlock as relu(W' x + t) with its norm folded in,
+        norm(W x) = s (W x) + t, s = gamma / sqrt(var + eps), t = beta - mean s (s = 1, t = 0 without a
+        norm), W' = s[:, None] W; then the last layer's weight row and bias.  Torch ops on the module's
+        device, no host read."""
+        if not self.foldable():
+            raise RuntimeError("MatchingNet1x1.folded: group, instance and train-mode batch norm need per-call "
+                               "statistics and cannot be folded into the weights")
+        weights, biases = [], []
+        for block in list(self)[:3]:
+            conv, norm = block[0], block[1]
+            w = conv.weight[:, :, 0, 0]
+            if isinstance(norm, nn.BatchNorm2d):
+                s = torch.rsqrt(norm.running_var + norm.eps)
+                if norm.affine:
+                    s = s * norm.weight
+                t = -norm.running_mean * s
+                if norm.affine:
+                    t = t + norm.bias
+                w = s[:, None] * w
+            else:
+                t = torch.zeros_like(w[:, 0])
+            weights.append(w)
+            biases.append(t)
+        weights.append(self[3].weight[0, :, 0, 0])
+        biases.append(self[3].bias)
+        return weights, biases
+
     def forward(self, mvol):
+        if isinstance(mvol, ops.StackSpec):       # fused path: the stack is never built
+            weights, biases = self.folded()
+            return ops.dicl_match_1x1(mvol.fmap1, mvol.fmap2, mvol.coords, mvol.radius, weights, biases,
+                                      precision=mvol.precision)
         b, du, dv, c2, h, w = mvol.shape
         cost = super().forward(mvol.view(b * du * dv, c2, h, w))
         return cost.view(b, du, dv, h, w)

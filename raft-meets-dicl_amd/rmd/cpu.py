@@ -23,7 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_head_args, check_loss_args, check_metric_args,
+from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_head_args, check_loss_args, check_match_args,
+                      check_metric_args,
                       pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
@@ -545,6 +546,20 @@ def local_cross_attn_backward(grad, q, k, v, win_y, win_x):
         return torch.autograd.grad(local_cross_attn(*ins, win_y, win_x), ins, grad.float())
 
 
+# ---- fused dicl-1x1 cost (corr/dicl_1x1.py:8-30, 51-79) --------------------------------------------
+
+def dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, compute):
+    """The stack, then the folded MatchingNet1x1 as 1x1 convolutions: fp32 whatever the compute mode."""
+    check_match_args(fmap1, fmap2, coords, radius, weights, biases, compute)
+    b, c, h, w = fmap1.shape
+    d = 2 * radius + 1
+    x = dicl_stack(fmap1.detach(), fmap2.detach(), coords.detach(), radius, 0, h, w, False).reshape(b * d * d, 2 * c, h, w)
+    for wt, t in zip(weights[:3], biases[:3]):
+        x = F.relu(F.conv2d(x, wt.detach().float()[:, :, None, None], t.detach().float().reshape(-1)))
+    x = F.conv2d(x, weights[3].detach().float().reshape(1, -1, 1, 1), biases[3].detach().float().reshape(1))
+    return x.view(b, d, d, h, w)
+
+
 # ---- registration ------------------------------------------------------------------------------
 #
 # The CPU kernel of an operator is the function of its name in this module.
@@ -554,5 +569,5 @@ assert all(_KERNELS.values()), f"every rmd operator needs a CPU kernel: {[n for 
 
 for _name, _fn in _KERNELS.items():
     LIB.impl(_name, _fn, "CPU")
-    if _name != "flow_metrics":         # not differentiable: library.py's Autograd kernel serves every device
+    if _name not in ("flow_metrics", "dicl_match_1x1"):     # not differentiable: library.py's Autograd kernel serves every device
         LIB.impl(_name, _fn, "AutogradCPU")

@@ -24,6 +24,8 @@ follow SURVEY.md §8(b):
   flow_metrics(estimates[], target, valid, distances[], ...) -> stats        metrics/epe.py, fl_all.py, aae.py, flow.py
   dicl_flow_head(cost, flow_coarse?, eps) -> (B, 3, h, w) flow + entropy     impls/dicl.py:31-85, 194-195, 202
   local_cross_attn(q, k, v, win_y, win_x) -> (B, cv, h, w)                   common/hsup.py:71-92
+  dicl_match_1x1(fmap1, fmap2, coords, radius, weights[], biases[],          corr/dicl_1x1.py:8-30, 51-79
+        compute) -> (B, 2r+1, 2r+1, h, w) cost
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -41,8 +43,8 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head" and "attn" are listed by loss_operators(),
-# metric_operators(), head_operators() and attn_operators().
+# set (operators()); "loss", "metric", "head", "attn" and "match" are listed by loss_operators(),
+# metric_operators(), head_operators(), attn_operators() and match_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -81,6 +83,8 @@ _OPS = {
     "local_cross_attn": ("attn", "(Tensor q, Tensor k, Tensor v, int win_y, int win_x) -> Tensor"),
     "local_cross_attn_backward": ("attn", "(Tensor grad, Tensor q, Tensor k, Tensor v, int win_y, int win_x) "
                                           "-> (Tensor, Tensor, Tensor)"),
+    "dicl_match_1x1": ("match", "(Tensor fmap1, Tensor fmap2, Tensor coords, int radius, Tensor[] weights, "
+                                "Tensor[] biases, int compute) -> Tensor"),
 }
 for _name, (_, _schema) in _OPS.items():
     LIB.define(_name + _schema)
@@ -113,6 +117,11 @@ def head_operators():
 def attn_operators():
     """Names of the registered torch.ops.rmd hidden-state upsampler (local cross-attention) operators."""
     return _family("attn")
+
+
+def match_operators():
+    """Names of the registered torch.ops.rmd fused matching-network operators."""
+    return _family("match")
 
 
 def _hip(name):
@@ -1076,3 +1085,84 @@ def _attn_bwd(ctx, grad):
 
 
 torch.library.register_autograd("rmd::local_cross_attn", _attn_bwd, setup_context=_attn_setup)
+
+
+# ---- fused dicl-1x1 cost: gather + folded 1x1 MatchingNet ------------------------------------------
+#
+# weights = [W1' (c1, 2C), W2' (c2, c1), W3' (c3, c2), w4 (c3 elements)], biases = [t1, t2, t3, b4 (1)]:
+# MatchingNet1x1 with its norm layers folded (rmd.blocks.dicl.MatchingNet1x1.folded()).  The HIP kernel
+# wants hidden widths that are multiples of 32 (rmd.ops.dicl_match_1x1 zero-pads); the CPU kernel takes
+# any.  Not differentiable: like flow_metrics, its Autograd kernel runs the backend kernel below autograd.
+
+MATCH_COMPUTE = (_lib.RMD_BF16X3, _lib.RMD_BF16)
+
+
+def check_match_args(fmap1, fmap2, coords, radius, weights, biases, compute):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of dicl_match_1x1;
+    returns the hidden widths (c1, c2, c3)."""
+    _check_fmaps(fmap1, fmap2)
+    b, c, h, w = fmap1.shape
+    if tuple(coords.shape) != (b, 2, h, w):
+        raise ValueError(f"dicl_match_1x1: coords must be ({b}, 2, {h}, {w}), got {tuple(coords.shape)}")
+    if min(b, c, h, w) < 1 or radius < 0:
+        raise ValueError(f"dicl_match_1x1: empty fmap {tuple(fmap1.shape)} or negative radius {radius}")
+    if len(weights) != 4 or len(biases) != 4:
+        raise ValueError(f"dicl_match_1x1: need 4 weights and 4 biases, got {len(weights)} and {len(biases)}")
+    if compute not in MATCH_COMPUTE:
+        raise ValueError(f"dicl_match_1x1: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    cin = 2 * c
+    for i in range(3):
+        if weights[i].dim() != 2 or weights[i].shape[1] != cin:
+            raise ValueError(f"dicl_match_1x1: weights[{i}] must be (c{i + 1}, {cin}), got {tuple(weights[i].shape)}")
+        cin = weights[i].shape[0]
+    widths = tuple(wt.shape[0] for wt in weights[:3])
+    for i, want in enumerate(widths + (1,)):
+        if biases[i].numel() != want:
+            raise ValueError(f"dicl_match_1x1: biases[{i}] must hold {want} elements, got {tuple(biases[i].shape)}")
+    if weights[3].numel() != cin:
+        raise ValueError(f"dicl_match_1x1: weights[3] must hold {cin} elements, got {tuple(weights[3].shape)}")
+    for t in (fmap1, fmap2, coords, *weights, *biases):
+        if not t.is_floating_point():
+            raise ValueError(f"dicl_match_1x1: tensors must be floating point, got {t.dtype}")
+    return widths
+
+
+def match_supported(channels, c1, c2, c3, radius):
+    """rmd_dicl_match_1x1_supported: whether the HIP kernel serves these sizes (host only)."""
+    return bool(_lib.lib().rmd_dicl_match_1x1_supported(channels, c1, c2, c3, radius))
+
+
+def _match_out(fmap1, radius):
+    b, _, h, w = fmap1.shape
+    d = 2 * radius + 1
+    return _like(fmap1, (b, d, d, h, w))
+
+
+@_hip("dicl_match_1x1")
+def _dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, compute):
+    c1, c2, c3 = check_match_args(fmap1, fmap2, coords, radius, weights, biases, compute)
+    b, c, h, w = fmap1.shape
+    if not match_supported(c, c1, c2, c3, radius):
+        raise ValueError(f"dicl_match_1x1: unsupported on the GPU: channels {c} (a multiple of 16 up to 64), hidden "
+                         f"widths {c1}, {c2}, {c3} (multiples of 32 up to 128), radius {radius} (1..4)")
+    f1, f2, co = _f32(fmap1), _f32(fmap2), _f32(coords)
+    ws, ts = [_f32(t) for t in weights], [_f32(t) for t in biases]
+    work = _lib.workspace("dicl_match_1x1", f1, c, c1, c2, c3, compute)
+    out = _match_out(f1, radius)
+    _lib.launch("rmd_dicl_match_1x1", f1, f1, f2, co, b, c, h, w, radius, ws[0], ts[0], ws[1], ts[1], ws[2], ts[2],
+                ws[3], ts[3], c1, c2, c3, compute, out, work)
+    return out
+
+
+@_fake("dicl_match_1x1")
+def _(fmap1, fmap2, coords, radius, weights, biases, compute):
+    check_match_args(fmap1, fmap2, coords, radius, weights, biases, compute)
+    return _match_out(fmap1, radius)
+
+
+def _dicl_match_1x1_below_autograd(fmap1, fmap2, coords, radius, weights, biases, compute):
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.rmd.dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, compute)
+
+
+LIB.impl("dicl_match_1x1", _dicl_match_1x1_below_autograd, "Autograd")

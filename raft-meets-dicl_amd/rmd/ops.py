@@ -428,6 +428,53 @@ def dicl_stack(fmap1, fmap2, coords, radius, level=0, norm_hw=None, extra_delta=
     return torch.ops.rmd.dicl_stack(fmap1, fmap2, coords, radius, level, int(nh), int(nw), bool(extra_delta))
 
 
+MATCH_PRECISIONS = {"fp32": RMD_BF16X3, "bf16": RMD_BF16}
+MATCH_WIDTH_STEP = 32      # the HIP kernel's hidden widths: whole 32-row MFMA tiles
+
+
+class StackSpec:
+    """What ops.dicl_stack would be called with, handed to MatchingNet1x1 instead of the stack itself: the
+    fused path computes the cost from it (dicl_match_1x1) and the stack is never built."""
+
+    __slots__ = ("fmap1", "fmap2", "coords", "radius", "precision")
+
+    def __init__(self, fmap1, fmap2, coords, radius, precision="fp32"):
+        self.fmap1, self.fmap2, self.coords, self.radius, self.precision = fmap1, fmap2, coords, radius, precision
+
+
+def match_padded_widths(weights):
+    """Hidden widths of folded MatchingNet1x1 weights after padding to whole MFMA tiles."""
+    return tuple(-(-w.shape[0] // MATCH_WIDTH_STEP) * MATCH_WIDTH_STEP for w in weights[:3])
+
+
+def _pad_match(weights, biases):
+    """Zero rows (and the matching zero columns of the next layer) up to the next multiple of 32: a padded
+    channel is relu(0 x + 0) = 0 and multiplies zero weights, so it adds nothing."""
+    ws, ts = [w.reshape(w.shape[0], -1) for w in weights[:3]] + [weights[3].reshape(1, -1)], list(biases)
+    for i, wide in enumerate(match_padded_widths(ws)):
+        extra = wide - ws[i].shape[0]
+        if extra:
+            ws[i] = torch.nn.functional.pad(ws[i], (0, 0, 0, extra))
+            ts[i] = torch.nn.functional.pad(ts[i].reshape(-1), (0, extra))
+            ws[i + 1] = torch.nn.functional.pad(ws[i + 1], (0, extra))
+    return ws[:3] + [ws[3].reshape(-1)], ts
+
+
+def dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, precision="fp32"):
+    """Fused dicl-1x1 cost (torch.ops.rmd.dicl_match_1x1; corr/dicl_1x1.py:8-30, 51-79): fmap1, fmap2
+    (B, C, h, w), coords (B, 2, h, w) -> (B, 2r+1, 2r+1, h, w), the displacement gather of ops.dicl_stack and
+    the folded MatchingNet1x1 (weights [W1', W2', W3', w4], biases [t1, t2, t3, b4] from
+    MatchingNet1x1.folded()) in one kernel.  precision "fp32": three split-bf16 products per layer (parity
+    mode); "bf16": one.  Not differentiable."""
+    if precision not in MATCH_PRECISIONS:
+        raise ValueError(f"dicl_match_1x1: unknown precision '{precision}', expected one of {sorted(MATCH_PRECISIONS)}")
+    weights, biases = list(weights), list(biases)
+    _same_device(fmap1, fmap2, coords, *weights, *biases)
+    if len(weights) == 4 and len(biases) == 4 and fmap1.device.type == "cuda":
+        weights, biases = _pad_match(weights, biases)
+    return torch.ops.rmd.dicl_match_1x1(fmap1, fmap2, coords, int(radius), weights, biases, MATCH_PRECISIONS[precision])
+
+
 def dicl_stack_int(fmap1, fmap2, ru, rv):
     """Integer-displacement matching volume with occlusion mask (torch.ops.rmd.dicl_stack_int;
     impls/dicl.py:212-238)."""
