@@ -10,7 +10,9 @@ product path (``raft-meets-dicl_amd/``) never imports it and has no CPU fallback
 """
 
 from .corr import (corr_volume, corr_pyramid, corr_lookup, corr_lookup_fs, corr_lookup_backward,
-                   corr_lookup_fs_backward, pyramid_level_shapes)
+                   corr_lookup_fs_backward, pyramid_level_shapes, corr_grad_geometry, corr_lookup_grad_levels,
+                   corr_grad_pack, corr_grad_unpack, corr_grad_pad_slots, corr_pool_targets,
+                   corr_unpool_targets)
 from .dicl import (dicl_stack, dicl_stack_at, dicl_stack_backward, dicl_stack_int, dicl_stack_int_at,
                    dicl_stack_int_backward, dap, dap_backward,
                    warp_backwards, warp_backwards_backward)
@@ -18,7 +20,8 @@ from .heads import up8, up8_backward, softargmax, softargmax_backward
 from .input import input_images, input_flow, pad_extents
 
 __all__ = ["corr_volume", "corr_pyramid", "corr_lookup", "corr_lookup_fs", "corr_lookup_backward",
-           "corr_lookup_fs_backward",
+           "corr_lookup_fs_backward", "corr_grad_geometry", "corr_lookup_grad_levels", "corr_grad_pack",
+           "corr_grad_unpack", "corr_grad_pad_slots", "corr_pool_targets", "corr_unpool_targets",
            "pyramid_level_shapes", "dicl_stack", "dicl_stack_at", "dicl_stack_backward", "dicl_stack_int",
            "dicl_stack_int_at",
            "dicl_stack_int_backward", "dap", "dap_backward", "up8", "up8_backward", "softargmax",

@@ -14,11 +14,17 @@ Reference semantics restated here (qzed/raft-meets-dicl v2):
   * a level with height or width 1 divides by zero in the [-1,1] normalisation
     (raft.py:73-74) and yields NaN for every query                   (fixture corr_b1_c16_12x20_nan)
   * raft/fs: fmap2 is avg-pooled instead of the volume, no 1/sqrt(C)  src/models/impls/raft_fs.py:13-87
+  * backward (autograd of raft.py:18-95), in the stages of include/rmd.h: the pyramid gradient G per
+    lookup (corr_lookup_grad_levels) in the chunked target order (corr_grad_pack / corr_grad_unpack),
+    the pooled targets P (corr_pool_targets), the unpooling (corr_unpool_targets); corr_lookup_backward
+    composes them.  A 1-pixel level carries no gradient.
 
 The bilinear lookup is restated in pixel coordinates (no [-1,1] round trip) with one weight set
 per query and level: all (2r+1)^2 offsets are integers, so every tap shares frac(x/2^i),
 frac(y/2^i).
 """
+
+import collections
 
 import numpy as np
 
@@ -192,54 +198,165 @@ def _sample_features(f, cx, cy, r, sx=1.0, sy=1.0):
     return out
 
 
-def corr_lookup_backward(fmap1, fmap2, coords, levels, radius, grad_out, mask_costs=()):
-    """d(sum(out*grad_out))/d(fmap1, fmap2) for raft.CorrBlock (dense restatement, small sizes).
+# ---- Backward of raft.CorrBlock, stage by stage (include/rmd.h, "Backward of the RAFT correlation") --
+#
+# G_l = d(sum(out * grad_out)) / d(pyramid level l) per lookup; all levels packed in the chunked order
+# of rmd.h as a (T' x N) matrix G; P = pooled fmap2 / sqrt(C) in the same target order; then
+#   grad_fmap1 = P G,   dP = fmap1 G^T,   grad_fmap2 = unpool(dP) / sqrt(C).
 
-    Transposes the lookup (bilinear scatter), the pooling (equal spread over each 2x2 block of
-    the floor-cropped region) and the GEMM.  Coordinates carry no gradient (raft.py:402).
+CorrGradGeometry = collections.namedtuple("CorrGradGeometry", "lh lw nch coff TC targets")
+
+# beyond this level coordinate no (2r+2)^2 patch meets a level (H, W < 16384): the query adds nothing
+_FAR = 30000.0
+
+
+def corr_grad_geometry(h, w, levels):
+    """Chunked target order of G (rmd.h): per level H_l, W_l, nch(l) = ceil(W_l / 8) chunks per target
+    row and coff(l) = sum_{l' < l} H_l' nch(l'), the first chunk; TC chunks and T' = 8 TC padded targets."""
+    lh = [h >> l for l in range(levels)]
+    lw = [w >> l for l in range(levels)]
+    nch = [-(-x // 8) for x in lw]
+    coff = [sum(lh[k] * nch[k] for k in range(l)) for l in range(levels)]
+    tc = sum(a * n for a, n in zip(lh, nch))
+    return CorrGradGeometry(lh, lw, nch, coff, tc, 8 * tc)
+
+
+def corr_lookup_grad_levels(coords, levels, radius, grad_out, mask_costs=(), dtype=None):
+    """Gradient of sum(out * grad_out) with respect to each pyramid level, for one lookup: a list of
+    (B, N, H_l, W_l) arrays (transpose of grid_sample at raft.py:80, zero padding per tap).
+
+    coords (B, 2, H, W); grad_out (B, L (2r+1)^2, H, W) in the lookup's channel order.  A level in
+    mask_costs (as l + 3, raft.py:86-87) and a level with H_l < 2 or W_l < 2 (NaN in the reference,
+    raft.py:73-74) are all zero.  A query whose level coordinate is NaN, +-inf or beyond +-30000 adds
+    nothing.  Arithmetic in ``dtype`` (default: grad_out's).
     """
-    b, c, h, w = fmap1.shape
-    d = 2 * radius + 1
+    dtype = np.dtype(grad_out.dtype if dtype is None else dtype)
+    b, _, h, w = coords.shape
     n = h * w
-    shapes = pyramid_level_shapes(h, w, levels)
-    g = grad_out.reshape(b, levels, d, d, n)                               # (B,L,a,b,P)
-    cx = coords[:, 0].reshape(b, n)
-    cy = coords[:, 1].reshape(b, n)
-    one = np.asarray(1, dtype=fmap1.dtype)
-    gcorr0 = np.zeros((b, n, h, w), dtype=fmap1.dtype)
-    bi = np.arange(b)[:, None]
-    pi = np.arange(n)[None, :]
-    for i, (hl, wl) in enumerate(shapes):
-        if i + 3 in mask_costs:
+    d, k = 2 * radius + 1, 2 * radius + 2
+    g = np.asarray(grad_out, dtype=dtype).reshape(b, levels, d, d, n)         # (B, L, a [x], b [y], N)
+    cx = np.asarray(coords[:, 0], dtype=dtype).reshape(b, n)
+    cy = np.asarray(coords[:, 1], dtype=dtype).reshape(b, n)
+    one = np.asarray(1, dtype=dtype)
+    bi = np.broadcast_to(np.arange(b)[:, None, None, None], (b, n, k, k))
+    pi = np.broadcast_to(np.arange(n)[None, :, None, None], (b, n, k, k))
+    out = []
+    for l, (hl, wl) in enumerate(pyramid_level_shapes(h, w, levels)):
+        gl = np.zeros((b, n, hl, wl), dtype=dtype)
+        out.append(gl)
+        if l + 3 in mask_costs or hl < 2 or wl < 2:
             continue
-        s = np.asarray(2.0 ** i, dtype=fmap1.dtype)
-        gl = np.zeros((b, n, hl, wl), dtype=fmap1.dtype)
+        s = np.asarray(2.0 ** l, dtype=dtype)
         lx, ly = cx / s, cy / s
-        x0 = np.floor(lx)
-        y0 = np.floor(ly)
-        fx, fy = lx - x0, ly - y0
-        x0 = x0.astype(np.int64)
-        y0 = y0.astype(np.int64)
-        for a in range(d):
-            for bb in range(d):
-                gv = g[:, i, a, bb, :]
-                for ddy, wy in ((0, one - fy), (1, fy)):
-                    for ddx, wx in ((0, one - fx), (1, fx)):
-                        xx = x0 + a - radius + ddx
-                        yy = y0 + bb - radius + ddy
-                        v = (xx >= 0) & (xx < wl) & (yy >= 0) & (yy < hl)
-                        np.add.at(gl, (bi, pi, np.clip(yy, 0, hl - 1), np.clip(xx, 0, wl - 1)),
-                                  gv * wx * wy * v)
-        # transpose of i successive 2x2 average pools: spread over 2^i x 2^i blocks
-        k = 2 ** i
-        up = np.repeat(np.repeat(gl, k, axis=-2), k, axis=-1) / np.asarray(k * k, dtype=gl.dtype)
-        gcorr0[..., : hl * k, : wl * k] += up
-    gcorr0 = gcorr0.reshape(b, n, n) / np.sqrt(np.asarray(c, dtype=fmap1.dtype))
-    f1 = fmap1.reshape(b, c, n)
-    f2 = fmap2.reshape(b, c, n)
-    gf1 = np.matmul(f2, gcorr0.transpose(0, 2, 1)).reshape(b, c, h, w)
-    gf2 = np.matmul(f1, gcorr0).reshape(b, c, h, w)
-    return gf1, gf2
+        far = ~(np.isfinite(lx) & np.isfinite(ly))
+        far |= (np.abs(np.where(far, 0, lx)) > _FAR) | (np.abs(np.where(far, 0, ly)) > _FAR)
+        lx, ly = np.where(far, 0, lx).astype(dtype), np.where(far, 0, ly).astype(dtype)
+        x0, y0 = np.floor(lx), np.floor(ly)
+        fx, fy = (lx - x0)[..., None, None], (ly - y0)[..., None, None]
+        # patch[j, i]: gradient at target (y0 - r + j, x0 - r + i), j, i = 0 .. 2r+1; tap (a, b) sits at
+        # (y0 - r + b, x0 - r + a) and spreads over the four corners with the forward's weights
+        gt = np.moveaxis(g[:, l], -1, 1).swapaxes(-1, -2)                     # (B, N, b [y], a [x])
+        patch = np.zeros((b, n, k, k), dtype=dtype)
+        patch[..., :-1, :-1] += (one - fy) * (one - fx) * gt
+        patch[..., :-1, 1:] += (one - fy) * fx * gt
+        patch[..., 1:, :-1] += fy * (one - fx) * gt
+        patch[..., 1:, 1:] += fy * fx * gt
+        offs = np.arange(k) - radius
+        yy = np.broadcast_to((y0.astype(np.int64)[..., None] + offs)[..., :, None], (b, n, k, k))
+        xx = np.broadcast_to((x0.astype(np.int64)[..., None] + offs)[..., None, :], (b, n, k, k))
+        v = (yy >= 0) & (yy < hl) & (xx >= 0) & (xx < wl) & ~far[..., None, None]
+        gl[bi[v], pi[v], yy[v], xx[v]] = patch[v]                             # one patch per query: no repeats
+    return out
+
+
+def corr_grad_pack(levels_list):
+    """Per-level (B, N, H_l, W_l) arrays -> G (B, TC, N, 8) in the chunked order of rmd.h: element
+    (b, target (l, y, x), query p) at ((b TC + coff(l) + y nch(l) + x / 8) N + p) 8 + x % 8; pad targets
+    (x >= W_l in a row's last chunk) are zero."""
+    parts = []
+    for gl in levels_list:
+        b, n, hl, wl = gl.shape
+        nch = -(-wl // 8)
+        pad = np.zeros((b, n, hl, nch * 8), dtype=gl.dtype)
+        pad[..., :wl] = gl
+        parts.append(pad.reshape(b, n, hl * nch, 8).transpose(0, 2, 1, 3))
+    return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+
+def corr_grad_unpack(G, b, h, w, levels):
+    """Inverse of corr_grad_pack: G (any shape of B TC N 8 elements) -> list of (B, N, H_l, W_l); the pad
+    slots are dropped (corr_grad_pad_slots names them)."""
+    geo = corr_grad_geometry(h, w, levels)
+    n = h * w
+    G = np.asarray(G).reshape(b, geo.TC, n, 8)
+    out = []
+    for l in range(levels):
+        hl, wl, nch = geo.lh[l], geo.lw[l], geo.nch[l]
+        blk = G[:, geo.coff[l]: geo.coff[l] + hl * nch].transpose(0, 2, 1, 3).reshape(b, n, hl, nch * 8)
+        out.append(np.ascontiguousarray(blk[..., :wl]))
+    return out
+
+
+def corr_grad_pad_slots(h, w, levels):
+    """(TC, 8) bool: True at the pad targets of the chunked order."""
+    geo = corr_grad_geometry(h, w, levels)
+    pad = np.zeros((geo.TC, 8), dtype=bool)
+    for l in range(levels):
+        rows = pad[geo.coff[l]: geo.coff[l] + geo.lh[l] * geo.nch[l]].reshape(geo.lh[l], geo.nch[l] * 8)
+        rows[:, geo.lw[l]:] = True
+    return pad
+
+
+def _target_rows(levels_list):
+    """Per-level (..., H_l, W_l) arrays -> (..., T') in the padded target order, pads zero."""
+    parts = []
+    for x in levels_list:
+        hl, wl = x.shape[-2:]
+        nch = -(-wl // 8)
+        pad = np.zeros(x.shape[:-1] + (nch * 8,), dtype=x.dtype)
+        pad[..., :wl] = x
+        parts.append(pad.reshape(x.shape[:-2] + (hl * nch * 8,)))
+    return np.concatenate(parts, axis=-1)
+
+
+def corr_pool_targets(fmap2, levels, scale):
+    """P (B, C, T') = avg_pool_{2^l}(fmap2) * scale for every level (successive 2x2 averages, floor
+    sizes: raft.py:35-47 applied to the feature map), in G's padded target order, pads zero."""
+    lv = [fmap2]
+    for _ in range(1, levels):
+        lv.append(_avg_pool2(lv[-1]))
+    s = np.asarray(scale, dtype=fmap2.dtype)
+    return _target_rows([x * s for x in lv])
+
+
+def corr_unpool_targets(dP, h, w, levels, scale):
+    """(B, C, T') -> (B, C, H, W): scale * sum_l avg_pool_{2^l}^T(level l of dP): every target spreads
+    1/4^l of its value over its 2^l x 2^l block of the floor-cropped map (avg_pool2d_backward)."""
+    geo = corr_grad_geometry(h, w, levels)
+    out = np.zeros(dP.shape[:-1] + (h, w), dtype=dP.dtype)
+    for l in range(levels):
+        hl, wl, nch = geo.lh[l], geo.lw[l], geo.nch[l]
+        x = dP[..., 8 * geo.coff[l]: 8 * (geo.coff[l] + hl * nch)].reshape(dP.shape[:-1] + (hl, nch * 8))[..., :wl]
+        k = 2 ** l
+        out[..., : hl * k, : wl * k] += np.repeat(np.repeat(x, k, axis=-2), k, axis=-1) / np.asarray(k * k, dtype=dP.dtype)
+    return out * np.asarray(scale, dtype=dP.dtype)
+
+
+def corr_lookup_backward(fmap1, fmap2, coords, levels, radius, grad_out, mask_costs=()):
+    """d(sum(out*grad_out))/d(fmap1, fmap2) for raft.CorrBlock, as the composition of the stages above:
+    grad_fmap1 = P G, dP = fmap1 G^T, grad_fmap2 = unpool(dP), with P and the unpooling scaled by
+    1/sqrt(C).  1-pixel levels (NaN in the reference's forward) carry no gradient.  Coordinates carry no
+    gradient (raft.py:402).  Dense, small sizes."""
+    b, c, h, w = fmap1.shape
+    n = h * w
+    dt = fmap1.dtype
+    gl = corr_lookup_grad_levels(coords, levels, radius, grad_out, mask_costs, dtype=dt)
+    G = corr_grad_pack(gl).transpose(0, 1, 3, 2).reshape(b, -1, n)              # (B, T', N)
+    scale = np.asarray(1, dtype=dt) / np.sqrt(np.asarray(c, dtype=dt))
+    P = corr_pool_targets(fmap2, levels, scale)                                  # (B, C, T')
+    gf1 = np.matmul(P, G).reshape(b, c, h, w)
+    dP = np.matmul(fmap1.reshape(b, c, n), G.transpose(0, 2, 1))                 # (B, C, T')
+    return gf1, corr_unpool_targets(dP, h, w, levels, scale)
 
 
 def corr_lookup_fs_backward(fmap1, fmap2, coords, levels, radius, grad_out, mask_costs=(), scale=None):

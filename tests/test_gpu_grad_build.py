@@ -1,7 +1,8 @@
 """rmd_corr_grad_build (corr_backward.hip): G of every lookup of a forward written in one pass must
 equal, bit for bit, the sequence of rmd_corr_lookup_backward calls into a zeroed G that it replaces
-(same per-lookup arithmetic, same summation order) — the sequential kernel is itself checked against
-the float64 oracle (test_gpu_corr.py backward tests), so this pins the build to the same oracle.
+(same per-lookup arithmetic, same summation order).  Both kernels share their arithmetic, so nothing
+here is independent of them: test_gpu_corr_backward_stages.py is where the sequential kernel and the
+build are each held to the float64 oracle of G (values, support, pad slots).
 Covers ragged query counts, widths not a multiple of 8, 1-pixel (NaN) levels, zeroed levels, every
 radius, more lookups than one launch holds (the accumulate path), coordinates far outside / NaN,
 accumulate = 1 into a non-zero G and the empty list."""
