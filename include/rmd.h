@@ -650,6 +650,43 @@ int rmd_dicl_match_1x1(const float* fmap1, const float* fmap2, const float* coor
                        const float* t2, const float* w3, const float* t3, const float* w4, const float* b4,
                        int c1, int c2, int c3, int compute, float* out, void* workspace, void* stream);
 
+/*
+ * Backward of rmd_dicl_match_1x1 (same tensors, shapes and folded parameters; b4 is not needed).  For
+ * every column x with upstream scalar g = grad_cost[b, a, bb, p] the forward is recomputed exactly as the
+ * forward kernel does it, and with a0 = x, z_l = W_l a_{l-1} + t_l, a_l = relu(z_l):
+ *   dz3 = (z3 > 0) ? w4 g : 0         gw4 += a3 g        gb4 += g
+ *   da_{l-1} = W_l^T dz_l             dz_{l-1} = (z_{l-1} > 0) ? da_{l-1} : 0
+ *   gW_l += dz_l a_{l-1}^T            gt_l += dz_l
+ *   grad_fmap1[:, p] += dx[0:C]       grad_fmap2 += bilinear adjoint of dx[C:2C] at the column's taps
+ * (zero padding per tap; a non-finite sample position scatters nothing; coordinates carry no gradient).
+ * The mask is z > 0 on the recomputed pre-activation, so a NaN pre-activation blocks the gradient as
+ * torch's ReLU backward does, while NaN activations still reach the weight gradients through 0 * NaN.
+ * Every matrix product is three split-bf16 MFMA products (hi.hi + hi.lo + lo.hi) with fp32 accumulation;
+ * dz3, the mask selects, gw4, gb4 and gt_l are fp32 VALU.  Only compute = RMD_BF16X3 has a backward: with
+ * one product per layer the recomputed masks differ from the exact ones on 2-4 % of the hidden units, so
+ * RMD_BF16 fails with RMD_ERR_ARG.  Supported shapes are the forward's
+ * (rmd_dicl_match_1x1_backward_supported, host only).  grad_fmap1 (B, C, h, w) or grad_fmap2 may be NULL
+ * to skip a feature gradient; the eight parameter-gradient pointers (shaped like their parameters,
+ * grad_b4 one float) are all given or all NULL.  Neither the stack nor a hidden activation or its
+ * gradient is written to memory: `workspace` (rmd_dicl_match_1x1_backward_workspace_bytes() bytes, 0 =
+ * unsupported arguments) holds the repacked weight fragments, plain and transposed, and one partial of
+ * the parameter gradients per workgroup.  grad_fmap1 and all parameter gradients are bitwise
+ * reproducible (partials written with plain stores, then added in a fixed order by a second kernel; no
+ * float atomics).  grad_fmap2 is zeroed and then accumulated with float atomics, as
+ * rmd_dicl_stack_backward's: its last bits depend on the order of the additions.  The launcher never
+ * allocates, frees or synchronises, and all argument checks run before any launch.
+ */
+int rmd_dicl_match_1x1_backward_supported(int channels, int c1, int c2, int c3, int radius);
+size_t rmd_dicl_match_1x1_backward_workspace_bytes(int batch, int channels, int height, int width, int radius,
+                                                   int c1, int c2, int c3);
+int rmd_dicl_match_1x1_backward(const float* grad_cost, const float* fmap1, const float* fmap2, const float* coords,
+                                int batch, int channels, int height, int width, int radius, const float* w1,
+                                const float* t1, const float* w2, const float* t2, const float* w3, const float* t3,
+                                const float* w4, int c1, int c2, int c3, int compute, float* grad_fmap1,
+                                float* grad_fmap2, float* grad_w1, float* grad_t1, float* grad_w2, float* grad_t2,
+                                float* grad_w3, float* grad_t3, float* grad_w4, float* grad_b4, void* workspace,
+                                void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

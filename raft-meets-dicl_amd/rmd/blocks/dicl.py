@@ -124,7 +124,7 @@ class MatchingNet1x1(nn.Sequential):
         if isinstance(mvol, ops.StackSpec):       # fused path: the stack is never built
             weights, biases = self.folded()
             return ops.dicl_match_1x1(mvol.fmap1, mvol.fmap2, mvol.coords, mvol.radius, weights, biases,
-                                      precision=mvol.precision)
+                                      precision=mvol.precision, differentiable=mvol.differentiable)
         b, du, dv, c2, h, w = mvol.shape
         cost = super().forward(mvol.view(b * du * dv, c2, h, w))
         return cost.view(b, du, dv, h, w)

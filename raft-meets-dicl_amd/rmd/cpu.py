@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_head_args, check_loss_args, check_match_args,
-                      check_metric_args,
+                      check_match_backward_args, check_metric_args,
                       pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
@@ -558,6 +558,30 @@ def dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, compute):
         x = F.relu(F.conv2d(x, wt.detach().float()[:, :, None, None], t.detach().float().reshape(-1)))
     x = F.conv2d(x, weights[3].detach().float().reshape(1, -1, 1, 1), biases[3].detach().float().reshape(1))
     return x.view(b, d, d, h, w)
+
+
+def dicl_match_1x1_train(fmap1, fmap2, coords, radius, weights, biases):
+    """The same composite with its ATen graph recorded (AutogradCPU): the stack, then 1x1 convolutions."""
+    check_match_args(fmap1, fmap2, coords, radius, weights, biases, _lib.RMD_BF16X3)
+    b, c, h, w = fmap1.shape
+    d = 2 * radius + 1
+    x = dicl_stack(fmap1.float(), fmap2.float(), coords.detach(), radius, 0, h, w, False).reshape(b * d * d, 2 * c, h, w)
+    for wt, t in zip(weights[:3], biases[:3]):
+        x = F.relu(F.conv2d(x, wt.float()[:, :, None, None], t.float().reshape(-1)))
+    x = F.conv2d(x, weights[3].float().reshape(1, -1, 1, 1), biases[3].float().reshape(1))
+    return x.view(b, d, d, h, w)
+
+
+def dicl_match_1x1_backward(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad):
+    """torch.autograd.grad of dicl_match_1x1_train's composite; (0,) tensors for a skipped group."""
+    check_match_backward_args(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad)
+    needs = [needs_grad[0], needs_grad[1]] + [needs_grad[2]] * 8
+    with torch.enable_grad():
+        ins = [t.detach().float().requires_grad_(True) for t in (fmap1, fmap2, *weights, *biases)]
+        out = dicl_match_1x1_train(ins[0], ins[1], coords.detach(), radius, ins[2:6], ins[6:10])
+        wanted = [t for t, need in zip(ins, needs) if need]
+        got = iter(torch.autograd.grad(out, wanted, grad.float()) if wanted else ())
+    return [next(got) if need else t.new_empty((0,)) for t, need in zip(ins, needs)]
 
 
 # ---- registration ------------------------------------------------------------------------------

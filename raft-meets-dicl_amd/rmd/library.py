@@ -26,6 +26,8 @@ follow SURVEY.md §8(b):
   local_cross_attn(q, k, v, win_y, win_x) -> (B, cv, h, w)                   common/hsup.py:71-92
   dicl_match_1x1(fmap1, fmap2, coords, radius, weights[], biases[],          corr/dicl_1x1.py:8-30, 51-79
         compute) -> (B, 2r+1, 2r+1, h, w) cost
+  dicl_match_1x1_train(fmap1, fmap2, coords, radius, weights[], biases[])    the same cost (fp32 mode), differentiable:
+        / dicl_match_1x1_backward(grad, ..., needs_grad) -> grads[]          its formula recomputes from the inputs
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -43,8 +45,9 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head", "attn" and "match" are listed by loss_operators(),
-# metric_operators(), head_operators(), attn_operators() and match_operators().
+# set (operators()); "loss", "metric", "head", "attn", "match" and "match_train" are listed by
+# loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators() and
+# match_train_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -85,6 +88,10 @@ _OPS = {
                                           "-> (Tensor, Tensor, Tensor)"),
     "dicl_match_1x1": ("match", "(Tensor fmap1, Tensor fmap2, Tensor coords, int radius, Tensor[] weights, "
                                 "Tensor[] biases, int compute) -> Tensor"),
+    "dicl_match_1x1_train": ("match_train", "(Tensor fmap1, Tensor fmap2, Tensor coords, int radius, "
+                                            "Tensor[] weights, Tensor[] biases) -> Tensor"),
+    "dicl_match_1x1_backward": ("match_train", "(Tensor grad, Tensor fmap1, Tensor fmap2, Tensor coords, int radius, "
+                                               "Tensor[] weights, Tensor[] biases, bool[] needs_grad) -> Tensor[]"),
 }
 for _name, (_, _schema) in _OPS.items():
     LIB.define(_name + _schema)
@@ -122,6 +129,11 @@ def attn_operators():
 def match_operators():
     """Names of the registered torch.ops.rmd fused matching-network operators."""
     return _family("match")
+
+
+def match_train_operators():
+    """Names of the registered torch.ops.rmd differentiable fused matching-network operators."""
+    return _family("match_train")
 
 
 def _hip(name):
@@ -1166,3 +1178,99 @@ def _dicl_match_1x1_below_autograd(fmap1, fmap2, coords, radius, weights, biases
 
 
 LIB.impl("dicl_match_1x1", _dicl_match_1x1_below_autograd, "Autograd")
+
+
+# ---- fused dicl-1x1 cost for training ---------------------------------------------------------------
+#
+# dicl_match_1x1_train is dicl_match_1x1 in its fp32 mode (the same HIP kernel, RMD_BF16X3: bitwise the same
+# cost) with an autograd formula that saves only its inputs; dicl_match_1x1_backward recomputes the MLP per
+# column (rmd_dicl_match_1x1_backward) and returns [grad_fmap1, grad_fmap2, gW1, gW2, gW3, gw4, gt1, gt2,
+# gt3, gb4], an empty tensor for every member of a group that needs_grad = [fmap1, fmap2, parameters]
+# switches off.  The one-product mode has no backward.  Coordinates carry no gradient.
+
+def match_backward_supported(channels, c1, c2, c3, radius):
+    """rmd_dicl_match_1x1_backward_supported: whether the HIP backward serves these sizes (host only)."""
+    return bool(_lib.lib().rmd_dicl_match_1x1_backward_supported(channels, c1, c2, c3, radius))
+
+
+def check_match_backward_args(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad):
+    """check_match_args plus the gradient's shape and the three needs_grad flags; returns the widths."""
+    widths = check_match_args(fmap1, fmap2, coords, radius, weights, biases, _lib.RMD_BF16X3)
+    b, _, h, w = fmap1.shape
+    d = 2 * radius + 1
+    if tuple(grad.shape) != (b, d, d, h, w) or not grad.is_floating_point():
+        raise ValueError(f"dicl_match_1x1_backward: grad must be a floating-point ({b}, {d}, {d}, {h}, {w}) tensor, "
+                         f"got {grad.dtype} {tuple(grad.shape)}")
+    if len(needs_grad) != 3:
+        raise ValueError(f"dicl_match_1x1_backward: needs_grad is [fmap1, fmap2, parameters], got {len(needs_grad)} flags")
+    return widths
+
+
+def _match_grads(fmap1, weights, biases, needs_grad):
+    """The ten gradients, shaped like what they belong to; (0,) for the members of a skipped group."""
+    shapes = [fmap1.shape, fmap1.shape] + [t.shape for t in weights] + [t.shape for t in biases]
+    needs = [needs_grad[0], needs_grad[1]] + [needs_grad[2]] * 8
+    return [_like(fmap1, tuple(s) if need else (0,)) for s, need in zip(shapes, needs)]
+
+
+def _match_unsupported(name, c, widths, radius):
+    return ValueError(f"{name}: unsupported on the GPU: channels {c} (a multiple of 16 up to 64), hidden widths "
+                      f"{widths[0]}, {widths[1]}, {widths[2]} (multiples of 32 up to 128), radius {radius} (1..4)")
+
+
+@_hip("dicl_match_1x1_train")
+def _dicl_match_1x1_train(fmap1, fmap2, coords, radius, weights, biases):
+    return _dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, _lib.RMD_BF16X3)
+
+
+@_fake("dicl_match_1x1_train")
+def _(fmap1, fmap2, coords, radius, weights, biases):
+    check_match_args(fmap1, fmap2, coords, radius, weights, biases, _lib.RMD_BF16X3)
+    return _match_out(fmap1, radius)
+
+
+@_hip("dicl_match_1x1_backward")
+def _dicl_match_1x1_backward(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad):
+    widths = check_match_backward_args(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad)
+    b, c, h, w = fmap1.shape
+    if not match_backward_supported(c, *widths, radius):
+        raise _match_unsupported("dicl_match_1x1_backward", c, widths, radius)
+    g, f1, f2, co = _f32(grad), _f32(fmap1), _f32(fmap2), _f32(coords)
+    ws, ts = [_f32(t) for t in weights], [_f32(t) for t in biases]
+    grads = _match_grads(f1, ws, ts, needs_grad)
+    if any(needs_grad):
+        work = _lib.workspace("dicl_match_1x1_backward", f1, b, c, h, w, radius, *widths)
+        gf1, gf2, gw1, gw2, gw3, gw4, gt1, gt2, gt3, gb4 = [t if t.numel() else None for t in grads]
+        _lib.launch("rmd_dicl_match_1x1_backward", f1, g, f1, f2, co, b, c, h, w, radius, ws[0], ts[0], ws[1], ts[1],
+                    ws[2], ts[2], ws[3], *widths, _lib.RMD_BF16X3, gf1, gf2, gw1, gt1, gw2, gt2, gw3, gt3, gw4, gb4,
+                    work)
+    return grads
+
+
+@_fake("dicl_match_1x1_backward")
+def _(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad):
+    check_match_backward_args(grad, fmap1, fmap2, coords, radius, weights, biases, needs_grad)
+    return _match_grads(fmap1, weights, biases, needs_grad)
+
+
+def _match_train_setup(ctx, inputs, output):
+    fmap1, fmap2, coords, radius, weights, biases = inputs
+    ctx.save_for_backward(fmap1, fmap2, coords, *weights, *biases)
+    ctx.radius = radius
+    ctx.param_needs = [t.requires_grad for t in (*weights, *biases)]
+    ctx.needs = [fmap1.requires_grad, fmap2.requires_grad, any(ctx.param_needs)]
+
+
+def _match_train_bwd(ctx, grad):
+    fmap1, fmap2, coords = ctx.saved_tensors[:3]
+    weights, biases = list(ctx.saved_tensors[3:7]), list(ctx.saved_tensors[7:11])
+    if not any(ctx.needs):
+        return None, None, None, None, [None] * 4, [None] * 4
+    grads = torch.ops.rmd.dicl_match_1x1_backward(grad, fmap1, fmap2, coords, ctx.radius, weights, biases, ctx.needs)
+    like = [fmap1, fmap2] + weights + biases
+    needs = ctx.needs[:2] + ctx.param_needs
+    out = [g.to(t.dtype) if need else None for g, t, need in zip(grads, like, needs)]
+    return out[0], out[1], None, None, out[2:6], out[6:10]
+
+
+torch.library.register_autograd("rmd::dicl_match_1x1_train", _match_train_bwd, setup_context=_match_train_setup)

@@ -436,10 +436,11 @@ class StackSpec:
     """What ops.dicl_stack would be called with, handed to MatchingNet1x1 instead of the stack itself: the
     fused path computes the cost from it (dicl_match_1x1) and the stack is never built."""
 
-    __slots__ = ("fmap1", "fmap2", "coords", "radius", "precision")
+    __slots__ = ("fmap1", "fmap2", "coords", "radius", "precision", "differentiable")
 
-    def __init__(self, fmap1, fmap2, coords, radius, precision="fp32"):
+    def __init__(self, fmap1, fmap2, coords, radius, precision="fp32", differentiable=False):
         self.fmap1, self.fmap2, self.coords, self.radius, self.precision = fmap1, fmap2, coords, radius, precision
+        self.differentiable = differentiable
 
 
 def match_padded_widths(weights):
@@ -460,18 +461,25 @@ def _pad_match(weights, biases):
     return ws[:3] + [ws[3].reshape(-1)], ts
 
 
-def dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, precision="fp32"):
+def dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, precision="fp32", differentiable=False):
     """Fused dicl-1x1 cost (torch.ops.rmd.dicl_match_1x1; corr/dicl_1x1.py:8-30, 51-79): fmap1, fmap2
     (B, C, h, w), coords (B, 2, h, w) -> (B, 2r+1, 2r+1, h, w), the displacement gather of ops.dicl_stack and
     the folded MatchingNet1x1 (weights [W1', W2', W3', w4], biases [t1, t2, t3, b4] from
     MatchingNet1x1.folded()) in one kernel.  precision "fp32": three split-bf16 products per layer (parity
-    mode); "bf16": one.  Not differentiable."""
+    mode); "bf16": one.  Not differentiable unless differentiable=True, which routes to
+    torch.ops.rmd.dicl_match_1x1_train: the same cost bit for bit (fp32 only), whose backward recomputes the
+    MLP per column (rmd_dicl_match_1x1_backward) and reaches fmap1, fmap2 and, through the padding here and
+    MatchingNet1x1.folded(), the raw parameters."""
     if precision not in MATCH_PRECISIONS:
         raise ValueError(f"dicl_match_1x1: unknown precision '{precision}', expected one of {sorted(MATCH_PRECISIONS)}")
+    if differentiable and precision != "fp32":
+        raise ValueError("dicl_match_1x1: the one-product mode has no backward (differentiable=True needs precision='fp32')")
     weights, biases = list(weights), list(biases)
     _same_device(fmap1, fmap2, coords, *weights, *biases)
     if len(weights) == 4 and len(biases) == 4 and fmap1.device.type == "cuda":
         weights, biases = _pad_match(weights, biases)
+    if differentiable:
+        return torch.ops.rmd.dicl_match_1x1_train(fmap1, fmap2, coords, int(radius), weights, biases)
     return torch.ops.rmd.dicl_match_1x1(fmap1, fmap2, coords, int(radius), weights, biases, MATCH_PRECISIONS[precision])
 
 
