@@ -6,14 +6,8 @@
 // weights (W', t) by the caller.  Neither the (B, d, d, 2C, h, w) stack nor any hidden activation is
 // written to memory.
 //
-// Orientation (one wave, v_mfma_f32_32x32x16_bf16): 32 samples — 32 consecutive pixels at ONE
-// displacement — sit on the MFMA column (lane & 31), channels on the row; weights are the A operand,
-// activations the B operand.  A layer's f32 accumulator tile (32 channels x 32 samples, 16 registers)
-// then IS two k-steps of the next layer's B operand after relu + cvt to bf16: registers 8s..8s+7 are
-// the fragment of k-step s, element j of lane half hh holding channel 16s + 8(j>>2) + 4hh + (j&3).
-// rmd_dicl_match_1x1's pack kernel writes every weight matrix as A fragments in that k order (bf16 hi
-// and, for RMD_BF16X3, the bf16 of the residual), and the first layer's B fragments are built in the
-// same order, so one fragment format serves all three layers.  No activation crosses lanes or LDS.
+// Orientation, fragment order, the weight pack kernel and the forward up to the layer-2 activations:
+// dicl_match_common.h, shared with the backward (dicl_match_grad.hip), which recomputes this forward.
 //
 // Work split: a work item is a strip of 32 pixels and a share of its (2r+1)^2 displacements; the 8 waves
 // of a (persistent) workgroup take displacements round-robin.  W1' x = W1a' f1[p] + W1b' f2sample: each
@@ -23,126 +17,19 @@
 // weight fragments live in LDS when they fit beside the biases (every mnet-scale <= 1 configuration
 // does), else they are read from global memory.  The last layer (c3 -> 1) and all biases are f32 VALU.
 
-#include "rmd_common.h"
+#include "dicl_match_common.h"
 
 #include <algorithm>
 
 namespace rmd {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
 constexpr int kThreads = 512, kWaves = kThreads / 64;
-constexpr int kMaxWidth = 128;                 // hidden widths and 2C
-constexpr int kBiasBytes = 4 * kMaxWidth * 4;  // t1, t2, t3, w4 in LDS
 constexpr int kLdsMax = 160 * 1024;
-constexpr int kCUs = 256;
 
-struct MatchParams {
-    int B, C, n, h, w, radius;
-    int kf;              // k-steps of one feature half: C / 16
-    int m1, m2, m3;      // 32-row tiles of the three hidden layers
-    int nfrag;           // A fragments (of 64 lanes x 8 bf16) of one part (hi or lo)
-    int nstrips;         // 32-pixel strips per batch image
+struct MatchParams : MatchGeom {
     int dsplit;          // workgroups sharing one strip's displacements
-    float sx, sy;        // (w-1)/(w-1), (h-1)/(h-1): 1, or NaN for a 1-pixel side, as the reference
 };
-
-// channel of element j of lane half hh in k-step ks (the accumulator-as-operand k order)
-__host__ __device__ __forceinline__ int frag_k(int ks, int hh, int j) { return 16 * ks + 8 * (j >> 2) + 4 * hh + (j & 3); }
-
-// ---- weights -> A fragments ------------------------------------------------------------------------
-// fragment (layer base + mo * ksteps + ks), lane l = (row 32 mo + (l & 31), half l >> 5), element j:
-// W[row][frag_k(ks, l >> 5, j)].  hi part first, then (parts == 2) the lo part.
-__global__ void __launch_bounds__(256)
-dicl_match_pack_kernel(const float* __restrict__ w1, const float* __restrict__ w2, const float* __restrict__ w3,
-                       MatchParams P, int parts, bf16x8* __restrict__ frags) {
-    const int id = blockIdx.x * 256 + threadIdx.x;
-    if (id >= P.nfrag * 64) return;
-    int f = id >> 6;
-    const int lane = id & 63;
-    const int n1 = P.m1 * 2 * P.kf, n2 = P.m2 * 2 * P.m1;
-    const float* wm;
-    int ksteps;
-    if (f < n1) { wm = w1; ksteps = 2 * P.kf; }
-    else if (f < n1 + n2) { wm = w2; ksteps = 2 * P.m1; f -= n1; }
-    else { wm = w3; ksteps = 2 * P.m2; f -= n1 + n2; }
-    const int mo = f / ksteps, ks = f - mo * ksteps;
-    const float* row = wm + (size_t)(32 * mo + (lane & 31)) * (16 * ksteps);
-    bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = row[frag_k(ks, lane >> 5, j)];
-        hi[j] = (__bf16)v;
-        lo[j] = (__bf16)(v - (float)hi[j]);
-    }
-    frags[id] = hi;
-    if (parts == 2) frags[(size_t)P.nfrag * 64 + id] = lo;
-}
-
-// ---- device helpers --------------------------------------------------------------------------------
-
-// bilinear, align_corners=True, zero padding per tap; a non-finite position samples NaN (dicl.hip's
-// make_taps_fwd, restated: the two kernels must agree on the sample, not share an object file)
-struct Taps {
-    int idx[4];
-    float wgt[4];
-};
-
-__device__ __forceinline__ Taps match_taps(float px, float py, int hl, int wl) {
-    Taps t;
-    const bool finite = __builtin_isfinite(px) && __builtin_isfinite(py);
-    px = fminf(fmaxf(px, -1.0e6f), 1.0e6f);
-    py = fminf(fmaxf(py, -1.0e6f), 1.0e6f);
-    const float fx0 = floorf(px), fy0 = floorf(py);
-    const float fx = px - fx0, fy = py - fy0;
-    const int x0 = (int)fx0, y0 = (int)fy0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
-        const bool ok = finite && xx >= 0 && xx < wl && yy >= 0 && yy < hl;
-        const float wx = (k & 1) ? fx : 1.f - fx;
-        const float wy = (k >> 1) ? fy : 1.f - fy;
-        t.idx[k] = ok ? yy * wl + xx : 0;
-        t.wgt[k] = finite ? (ok ? wx * wy : 0.f) : __builtin_nanf("");
-    }
-    return t;
-}
-
-// torch's relu keeps NaN (fmaxf(x, 0) would drop it): IEEE maximum, one v_maximum3_f32
-__device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
-
-// a float at a 32-bit byte offset from a wave-uniform base (scalar base + vector offset addressing)
-__device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-// frag_k without the lane-half term: the wave-uniform part of a fragment element's channel
-__device__ __forceinline__ int frag_k_uniform(int ks, int j) { return 16 * ks + 8 * (j >> 2) + (j & 3); }
-
-template <int NP>
-__device__ __forceinline__ void split8(const float* v, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (__bf16)v[j];
-        if constexpr (NP == 3) lo[j] = (__bf16)(v[j] - (float)hi[j]);
-    }
-}
-
-// acc += A . B with NP bf16 products: hi.hi, and for NP == 3 also lo.hi and hi.lo (small terms first)
-template <int NP>
-__device__ __forceinline__ void mma(f32x16& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh,
-                                    const bf16x8& bl) {
-    if constexpr (NP == 3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-}
-
-// accumulator row of register i for lane half hh (32x32 C/D map)
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
 
 // NP: bf16 products per layer.  WLDS: weight fragments staged in LDS.  KF, M1..M3: compile-time bounds of
 // the k-step / tile loops (register arrays); EXACT: they are the sizes themselves, else P's sizes guard.
@@ -160,12 +47,7 @@ dicl_match_kernel(const float* __restrict__ f1, const float* __restrict__ f2, co
     const int r = lane & 31, hh = lane >> 5;
     const int kf = EXACT ? KF : P.kf, m1 = EXACT ? M1 : P.m1, m2 = EXACT ? M2 : P.m2, m3 = EXACT ? M3 : P.m3;
 
-    for (int i = tid; i < 4 * kMaxWidth; i += kThreads) {
-        const int which = i / kMaxWidth, c = i - which * kMaxWidth;
-        const float* src = which == 0 ? t1 : which == 1 ? t2 : which == 2 ? t3 : w4;
-        const int width = 32 * (which == 0 ? m1 : which == 1 ? m2 : m3);
-        sb[i] = c < width ? src[c] : 0.f;
-    }
+    stage_biases(sb, t1, t2, t3, w4, m1, m2, m3, tid, kThreads);
     if constexpr (WLDS) {
         bf16x8* dst = reinterpret_cast<bf16x8*>(sm + kBiasBytes);
         const int total = P.nfrag * 64 * (NP == 3 ? 2 : 1);
@@ -179,7 +61,7 @@ dicl_match_kernel(const float* __restrict__ f1, const float* __restrict__ f2, co
         if constexpr (WLDS) return sfr[i];
         else return frags[i];
     };
-    const int fb1 = 0, fb2 = m1 * 2 * kf, fb3 = fb2 + m2 * 2 * m1;   // fragment base of each layer
+    const int fb2 = m1 * 2 * kf, fb3 = fb2 + m2 * 2 * m1;   // fragment base of layers 2, 3 (layer 1: 0)
 
     const int d = 2 * P.radius + 1, dd = d * d;
     const int n = P.n;
@@ -201,104 +83,28 @@ dicl_match_kernel(const float* __restrict__ f1, const float* __restrict__ f2, co
         f32x16 base[M1];
         {
             bf16x8 xh[KF], xl[KF];
-#pragma unroll
-            for (int ks = 0; ks < KF; ++ks) {
-                if (EXACT || ks < kf) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = ld_off(f1b + (size_t)frag_k_uniform(ks, j) * n, off1);
-                    split8<NP>(v, xh[ks], xl[ks]);
-                }
-            }
-#pragma unroll
-            for (int mo = 0; mo < M1; ++mo) {
-                if (EXACT || mo < m1) {
-                    f32x16 acc;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[i] = sb[32 * mo + acc_row(i, hh)];
-#pragma unroll
-                    for (int ks = 0; ks < KF; ++ks) {
-                        if (EXACT || ks < kf) {
-                            const int f = fb1 + mo * 2 * kf + ks;
-                            mma<NP>(acc, afrag(f, 0), NP == 3 ? afrag(f, 1) : bf16x8{}, xh[ks], xl[ks]);
-                        }
-                    }
-                    base[mo] = acc;
-                }
-            }
+            f1_frags<NP, EXACT, KF>(f1b, n, off1, kf, xh, xl);
+            layer1_base<NP, EXACT, KF, M1>(base, afrag, sb, kf, m1, hh, xh, xl);
         }
 
         for (int disp = part * kWaves + wave; disp < dd; disp += kWaves * P.dsplit) {
             const int a = disp / d, bb = disp - a * d;
             const float px = (cx + (float)(a - P.radius)) * P.sx;
             const float py = (cy + (float)(bb - P.radius)) * P.sy;
-            const Taps t = match_taps(px, py, P.h, P.w);
-            unsigned off2[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) off2[k] = (half_off + (unsigned)t.idx[k]) * 4u;
-
-            // f2 half of the column: bilinear samples, straight into layer-1 B fragments
-            bf16x8 xh[KF], xl[KF];
-#pragma unroll
-            for (int ks = 0; ks < KF; ++ks) {
-                if (EXACT || ks < kf) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float* fc = f2b + (size_t)frag_k_uniform(ks, j) * n;      // wave-uniform
-                        v[j] = t.wgt[0] * ld_off(fc, off2[0]) + t.wgt[1] * ld_off(fc, off2[1]) +
-                               t.wgt[2] * ld_off(fc, off2[2]) + t.wgt[3] * ld_off(fc, off2[3]);
-                    }
-                    split8<NP>(v, xh[ks], xl[ks]);
-                }
-            }
-
-            // layer 1 (f2 half on top of base) -> layer-2 B fragments
-            bf16x8 yh[2 * M1], yl[2 * M1];
-#pragma unroll
-            for (int mo = 0; mo < M1; ++mo) {
-                if (EXACT || mo < m1) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    f32x16 acc = base[mo];
-#pragma unroll
-                    for (int ks = 0; ks < KF; ++ks) {
-                        if (EXACT || ks < kf) {
-                            const int f = fb1 + mo * 2 * kf + kf + ks;
-                            mma<NP>(acc, afrag(f, 0), NP == 3 ? afrag(f, 1) : bf16x8{}, xh[ks], xl[ks]);
-                        }
-                    }
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = relu_nan(acc[8 * s + j]);
-                        split8<NP>(v, yh[2 * mo + s], yl[2 * mo + s]);
-                    }
-                }
-            }
-
-            // layer 2 -> layer-3 B fragments
-            bf16x8 zh[2 * M2], zl[2 * M2];
+            const Taps t = make_taps_fwd(px, py, P.h, P.w);
+            bf16x8 xh[KF], xl[KF], yh[2 * M1], yl[2 * M1], zh[2 * M2], zl[2 * M2];
+            f2_frags<NP, EXACT, KF>(f2b, n, half_off, t, kf, xh, xl);
+            layer1<NP, EXACT, false, KF, M1>(base, afrag, kf, m1, hh, xh, xl, yh, yl, nullptr);
+            // layer 2 -> layer-3 B fragments: the loop of dicl_match_common.h's layer2(), kept here.  Called as
+            // that function, the EXACT instances take 240 / 164 VGPRs instead of 186 / 140 (the bf16 one 4 below
+            // the limit of its 3 waves per SIMD)
 #pragma unroll
             for (int mo = 0; mo < M2; ++mo) {
                 if (EXACT || mo < m2) {
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16 acc = {};
-#pragma unroll
-                    for (int ks = 0; ks < 2 * M1; ++ks) {
-                        if (EXACT || ks < 2 * m1) {
-                            const int f = fb2 + mo * 2 * m1 + ks;
-                            mma<NP>(acc, afrag(f, 0), NP == 3 ? afrag(f, 1) : bf16x8{}, yh[ks], yl[ks]);
-                        }
-                    }
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j)
-                            v[j] = relu_nan(acc[8 * s + j] + sb[kMaxWidth + 32 * mo + acc_row(8 * s + j, hh)]);
-                        split8<NP>(v, zh[2 * mo + s], zl[2 * mo + s]);
-                    }
+                    mma_tile<NP, EXACT, 2 * M1>(acc, afrag, fb2 + mo * 2 * m1, 0, 2 * m1, yh, yl);
+                    relu_frags<NP, true, false>(acc, sb + kMaxWidth + 32 * mo, hh, zh + 2 * mo, zl + 2 * mo);
                 }
             }
 
@@ -309,13 +115,7 @@ dicl_match_kernel(const float* __restrict__ f1, const float* __restrict__ f2, co
                 if (EXACT || mo < m3) {
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16 acc = {};
-#pragma unroll
-                    for (int ks = 0; ks < 2 * M2; ++ks) {
-                        if (EXACT || ks < 2 * m2) {
-                            const int f = fb3 + mo * 2 * m2 + ks;
-                            mma<NP>(acc, afrag(f, 0), NP == 3 ? afrag(f, 1) : bf16x8{}, zh[ks], zl[ks]);
-                        }
-                    }
+                    mma_tile<NP, EXACT, 2 * M2>(acc, afrag, fb3 + mo * 2 * m2, 0, 2 * m2, zh, zl);
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int row = 32 * mo + acc_row(i, hh);
@@ -329,36 +129,24 @@ dicl_match_kernel(const float* __restrict__ f1, const float* __restrict__ f2, co
     }
 }
 
-bool width_ok(int c) { return c >= 32 && c <= kMaxWidth && c % 32 == 0; }
-
-bool match_supported(int channels, int c1, int c2, int c3, int radius) {
-    return channels >= 16 && channels % 16 == 0 && 2 * channels <= kMaxWidth && width_ok(c1) && width_ok(c2) &&
-           width_ok(c3) && radius >= 1 && radius <= 4;
-}
-
-int match_nfrag(int channels, int c1, int c2, int c3) {
-    return (c1 / 32) * (2 * channels / 16) + (c2 / 32) * (c1 / 16) + (c3 / 32) * (c2 / 16);
-}
-
 template <int NP>
 int launch_match(const float* f1, const float* f2, const float* coords, const bf16x8* frags, const float* t1,
                  const float* t2, const float* t3, const float* w4, const float* b4, const MatchParams& P, int grid,
                  bool wlds, size_t lds, float* out, hipStream_t st) {
-#define RMD_MATCH(WLDS, EX, KF, M1, M2, M3)                                                                    \
-    do {                                                                                                        \
-        auto k = dicl_match_kernel<NP, WLDS, EX, KF, M1, M2, M3>;                                               \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)lds);                                                                   \
-        k<<<grid, kThreads, lds, st>>>(f1, f2, coords, frags, t1, t2, t3, w4, b4, P, out);                      \
-    } while (0)
-    // the two shapes of the reference's configurations have loops of their own size (they always fit LDS);
-    // everything else runs the 4-tile loops guarded by the sizes, weights from global memory past LDS
-    // (three-product mode only: the widest one-product fragment set is 96 KB)
-    if (P.kf == 2 && P.m1 == 3 && P.m2 == 4 && P.m3 == 2) RMD_MATCH(true, true, 2, 3, 4, 2);         // C = 32, mnet scale 1
-    else if (P.kf <= 2 && P.m1 <= 2 && P.m2 <= 2 && P.m3 <= 1) RMD_MATCH(true, false, 2, 2, 2, 1);   // mnet scale 0.5
-    else if (wlds) RMD_MATCH(true, false, 4, 4, 4, 4);
-    else if constexpr (NP == 3) RMD_MATCH(false, false, 4, 4, 4, 4);
-    else RMD_REQUIRE(false, RMD_ERR_SHAPE, "rmd_dicl_match_1x1: one-product weight fragments always fit LDS");
+#define RMD_MATCH(WLDS, EX, KF, M1, M2, M3)                                                                       \
+    launch_lds(dicl_match_kernel<NP, WLDS, EX, KF, M1, M2, M3>, grid, kThreads, lds, st, f1, f2, coords, frags, t1, \
+               t2, t3, w4, b4, P, out)
+    // the exact and the 2/2/2/1 class always fit LDS; the 4-tile loops read the weights from global memory
+    // past LDS (three-product mode only: the widest one-product fragment set is 96 KB)
+    switch (match_class(P)) {
+    case MatchClass::kExact2342: RMD_MATCH(true, true, 2, 3, 4, 2); break;
+    case MatchClass::kGuarded2221: RMD_MATCH(true, false, 2, 2, 2, 1); break;
+    case MatchClass::kGuarded4444:
+        if (wlds) RMD_MATCH(true, false, 4, 4, 4, 4);
+        else if constexpr (NP == 3) RMD_MATCH(false, false, 4, 4, 4, 4);
+        else RMD_REQUIRE(false, RMD_ERR_SHAPE, "rmd_dicl_match_1x1: one-product weight fragments always fit LDS");
+        break;
+    }
 #undef RMD_MATCH
     return check_launch("rmd_dicl_match_1x1");
 }
@@ -386,31 +174,18 @@ extern "C" int rmd_dicl_match_1x1(const float* fmap1, const float* fmap2, const 
                 RMD_ERR_ARG, "rmd_dicl_match_1x1: null pointer");
     RMD_REQUIRE(compute == RMD_BF16X3 || compute == RMD_BF16, RMD_ERR_ARG,
                 "rmd_dicl_match_1x1: compute must be RMD_BF16X3 or RMD_BF16, got %d", compute);
-    RMD_REQUIRE(batch > 0 && height > 0 && width > 0, RMD_ERR_SHAPE, "rmd_dicl_match_1x1: bad sizes");
-    RMD_REQUIRE(match_supported(channels, c1, c2, c3, radius), RMD_ERR_SHAPE,
-                "rmd_dicl_match_1x1: unsupported (channels=%d widths=%d,%d,%d radius=%d): channels a multiple of 16 "
-                "up to 64, widths multiples of 32 up to 128, radius 1..4", channels, c1, c2, c3, radius);
-    const long long n = (long long)height * width;
-    // 32-bit lane offsets into one image's feature map, 64-bit everywhere else (the output included)
-    RMD_REQUIRE(n * channels < (1ll << 30), RMD_ERR_SHAPE, "rmd_dicl_match_1x1: %lld pixels x %d channels per image",
-                n, channels);
+    if (int rc = match_check_shape("rmd_dicl_match_1x1", batch, channels, height, width, radius, c1, c2, c3)) return rc;
     MatchParams P;
-    P.B = batch; P.C = channels; P.n = (int)n; P.h = height; P.w = width; P.radius = radius;
-    P.kf = channels / 16; P.m1 = c1 / 32; P.m2 = c2 / 32; P.m3 = c3 / 32;
-    P.nfrag = match_nfrag(channels, c1, c2, c3);
-    P.nstrips = (int)((n + 31) / 32);
-    // 0/0 -> NaN for a 1-pixel side, exactly as the reference's normalisation (rmd_dicl_stack)
-    P.sx = (float)(width - 1) / (float)(width - 1);
-    P.sy = (float)(height - 1) / (float)(height - 1);
+    static_cast<MatchGeom&>(P) = match_geom(batch, channels, height, width, radius, c1, c2, c3);
     const long long strips = (long long)batch * P.nstrips;
     const int dd = (2 * radius + 1) * (2 * radius + 1);
     // few strips: several workgroups share one strip's displacements, so that every CU has work
     P.dsplit = (int)std::min<long long>(std::max<long long>(kCUs / strips, 1), (dd + kWaves - 1) / kWaves);
     const int grid = (int)std::min<long long>(strips * P.dsplit, kCUs);
-    const int parts = compute == RMD_BF16X3 ? 2 : 1;
+    const int parts = compute == RMD_BF16X3 ? 2 : 1;      // hi, and the lo part of the three-product mode
     hipStream_t st = as_stream(stream);
     bf16x8* frags = reinterpret_cast<bf16x8*>(workspace);
-    dicl_match_pack_kernel<<<(P.nfrag * 64 + 255) / 256, 256, 0, st>>>(w1, w2, w3, P, parts, frags);
+    match_pack<1>(match_pack_desc(w1, w2, w3, channels, c1, c2, c3, 1), P.nfrag, parts == 2, frags, st);
     const size_t wbytes = (size_t)P.nfrag * 64 * sizeof(bf16x8) * parts;
     const bool wlds = kBiasBytes + wbytes <= (size_t)kLdsMax;
     const size_t lds = kBiasBytes + (wlds ? wbytes : 0);

@@ -1,13 +1,14 @@
 // dicl_match_grad.hip — backward of the fused dicl-1x1 cost (dicl_match.hip): recomputes the MLP per column
 // on the MFMA pipe and never writes the (B, d, d, 2C, h, w) stack, a hidden activation or its gradient.
 //
-// Orientation as the forward kernel: a wave owns a column set — 32 consecutive pixels at ONE displacement —
-// with the samples on the MFMA column (lane & 31) and channels on the row.  The forward is recomputed as
-// dicl_match_kernel<3> does it (same taps, same three split-bf16 products, same fragment order), keeping a
-// 16-bit mask (z > 0) per accumulator tile.  dz_l is built on the VALU in the accumulator layout of z_l, so
-// after the split to bf16 hi / lo it is two k-steps of the B operand of W_l^T dz_l, with W_l^T packed as A
-// fragments in the same k order; the result lands in the layout of z_{l-1}, where the mask applies in
-// registers.  Every product is hi.hi + hi.lo + lo.hi with fp32 accumulation.
+// Orientation and fragment order as the forward kernel (dicl_match_common.h): a wave owns a column set — 32
+// consecutive pixels at ONE displacement — with the samples on the MFMA column (lane & 31) and channels on
+// the row.  The forward is recomputed by the forward kernel's own templates in their three-product mode
+// (same taps, same three split-bf16 products, same fragment order), keeping a 16-bit mask (z > 0) per
+// accumulator tile.  dz_l is built on the VALU in the accumulator layout of z_l, so after the split to bf16
+// hi / lo it is two k-steps of the B operand of W_l^T dz_l, with W_l^T packed as A fragments in the same k
+// order; the result lands in the layout of z_{l-1}, where the mask applies in registers.  Every product is
+// hi.hi + hi.lo + lo.hi with fp32 accumulation.
 //
 // Weight gradients gW_l = dz_l a_{l-1}^T need the samples on K.  A workgroup is 4 waves (one per SIMD, the
 // whole register file each); per round every wave takes one displacement of the workgroup's strip and
@@ -22,128 +23,31 @@
 // whole strip): bitwise reproducible.  grad_fmap2 is the bilinear adjoint of dx[C:2C] on float atomics, as
 // rmd_dicl_stack_backward's.
 //
+// Resources: every instance runs at 512 registers and spills — 4872 / 728 / 5736 B of scratch per lane for the
+// exact, 2/2/2/1 and 4/4/4/4 instances (times in profiles/dicl_match_share_r14.json).
+//
 // A lane without a column of its own (a strip remainder, a wave past the last displacement) runs with
 // g = 0 and stages zeros, so it adds nothing anywhere — not even 0 * NaN.
 
-#include "rmd_common.h"
+#include "dicl_match_common.h"
 
 #include <algorithm>
 
 namespace rmd {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
 constexpr int kThreads = 256, kWaves = kThreads / 64;
-constexpr int kMaxWidth = 128;                         // hidden widths and 2C
-constexpr int kBiasBytes = 4 * kMaxWidth * 4;          // t1, t2, t3, w4 in LDS
 constexpr int kStagePart = kMaxWidth * 32 * 2;         // one [channel][32 samples] bf16 array
 constexpr int kStageWave = 4 * kStagePart;             // dz hi | dz lo | a hi | a lo of one wave
 constexpr int kRedStride = 33;                         // wave-private [32 rows][32 samples] f32, padded
 constexpr int kRedWave = 32 * kRedStride * 4;
 constexpr int kLdsBytes = kBiasBytes + kWaves * (kStageWave + kRedWave);
-constexpr int kCUs = 256;
 static_assert(kLdsBytes <= 160 * 1024, "LDS budget");
 
-struct GradParams {
-    int B, C, n, h, w, radius;
-    int kf;              // k-steps of one feature half: C / 16 (= 32-row tiles of the 2C input rows)
-    int m1, m2, m3;      // 32-row tiles of the three hidden layers
-    int nfrag;           // A fragments of one part (hi or lo) of one orientation (plain or transposed)
-    int nstrips;         // 32-pixel strips per batch image
+struct GradParams : MatchGeom {
     int nw, nv;          // floats of one partial: the three matrices; gw4 | gt1 | gt2 | gt3 | gb4
     int params;          // parameter gradients wanted
-    float sx, sy;
 };
-
-// the six matrices of the pack kernel: A[row][k] = src[row * row_stride + k * k_stride]
-struct PackDesc {
-    const float* src[6];
-    int row_stride[6], k_stride[6], ksteps[6], first[7];
-};
-
-// channel of element j of lane half hh in k-step ks (the accumulator-as-operand k order, dicl_match.hip)
-__host__ __device__ __forceinline__ int frag_k(int ks, int hh, int j) { return 16 * ks + 8 * (j >> 2) + 4 * hh + (j & 3); }
-__device__ __forceinline__ int frag_k_uniform(int ks, int j) { return 16 * ks + 8 * (j >> 2) + (j & 3); }
-// accumulator row of register i for lane half hh (32x32 C/D map)
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
-
-// W1, W2, W3 as in dicl_match_pack_kernel (matrices 0..2), then W1^T, W2^T, W3^T (3..5): fragment
-// (first[m] + mo * ksteps + ks), lane l = (row 32 mo + (l & 31), half l >> 5), element j:
-// A[row][frag_k(ks, l >> 5, j)].  Parts: plain hi, plain lo, transposed hi, transposed lo, nfrag each.
-__global__ void __launch_bounds__(256)
-dicl_match_grad_pack_kernel(PackDesc D, int nfrag, bf16x8* __restrict__ frags) {
-    const int id = blockIdx.x * 256 + threadIdx.x;
-    if (id >= 2 * nfrag * 64) return;
-    const int fa = id >> 6, lane = id & 63;
-    int m = 0;
-    while (fa >= D.first[m + 1]) ++m;
-    const int f = fa - D.first[m];
-    const int mo = f / D.ksteps[m], ks = f - mo * D.ksteps[m];
-    const float* row = D.src[m] + (size_t)(32 * mo + (lane & 31)) * D.row_stride[m];
-    bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = row[(size_t)frag_k(ks, lane >> 5, j) * D.k_stride[m]];
-        hi[j] = (__bf16)v;
-        lo[j] = (__bf16)(v - (float)hi[j]);
-    }
-    // first[3] == nfrag: plain fragments fill parts 0 / 1, transposed ones parts 2 / 3
-    const int orient = fa >= nfrag ? 1 : 0;
-    const size_t at = ((size_t)(2 * orient) * nfrag + (fa - orient * nfrag)) * 64 + lane;
-    frags[at] = hi;
-    frags[at + (size_t)nfrag * 64] = lo;
-}
-
-// bilinear taps as dicl_match.hip's match_taps; `bwd`: a non-finite position has zero weights (it
-// scatters nothing), else NaN weights (it samples NaN)
-struct Taps {
-    int idx[4];
-    float wgt[4];
-};
-
-__device__ __forceinline__ Taps match_taps(float px, float py, int hl, int wl, bool bwd) {
-    Taps t;
-    const bool finite = __builtin_isfinite(px) && __builtin_isfinite(py);
-    px = fminf(fmaxf(px, -1.0e6f), 1.0e6f);
-    py = fminf(fmaxf(py, -1.0e6f), 1.0e6f);
-    const float fx0 = floorf(px), fy0 = floorf(py);
-    const float fx = px - fx0, fy = py - fy0;
-    const int x0 = (int)fx0, y0 = (int)fy0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
-        const bool ok = finite && xx >= 0 && xx < wl && yy >= 0 && yy < hl;
-        const float wx = (k & 1) ? fx : 1.f - fx;
-        const float wy = (k >> 1) ? fy : 1.f - fy;
-        t.idx[k] = ok ? yy * wl + xx : 0;
-        t.wgt[k] = finite ? (ok ? wx * wy : 0.f) : (bwd ? 0.f : __builtin_nanf(""));
-    }
-    return t;
-}
-
-__device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
-
-__device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-__device__ __forceinline__ void split8(const float* v, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (__bf16)v[j];
-        lo[j] = (__bf16)(v[j] - (float)hi[j]);
-    }
-}
-
-// acc += A . B: lo.hi, hi.lo, then hi.hi (small terms first, as the forward)
-__device__ __forceinline__ void mma3(f32x16& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh,
-                                     const bf16x8& bl) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-}
 
 // LDS traffic between the lanes of ONE wave: DS operations of a wave execute in order; the fences keep
 // the compiler from moving them and wait for the data
@@ -201,7 +105,7 @@ __device__ __forceinline__ void wgrad(f32x16 (&acc)[S], int tiles, int ncol, int
                     const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + kStagePart + ao);
                     const bf16x8 bh = *reinterpret_cast<const bf16x8*>(base + 2 * kStagePart + bo);
                     const bf16x8 bl = *reinterpret_cast<const bf16x8*>(base + 3 * kStagePart + bo);
-                    mma3(acc[s], ah, al, bh, bl);
+                    mma<3>(acc[s], ah, al, bh, bl);
                 }
             }
         }
@@ -244,18 +148,13 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
     const int kf = EXACT ? KF : P.kf, m1 = EXACT ? M1 : P.m1, m2 = EXACT ? M2 : P.m2, m3 = EXACT ? M3 : P.m3;
     const bool params = P.params != 0;
 
-    for (int i = tid; i < 4 * kMaxWidth; i += kThreads) {
-        const int which = i / kMaxWidth, c = i - which * kMaxWidth;
-        const float* src = which == 0 ? t1 : which == 1 ? t2 : which == 2 ? t3 : w4;
-        const int width = 32 * (which == 0 ? m1 : which == 1 ? m2 : m3);
-        sb[i] = c < width ? src[c] : 0.f;
-    }
+    stage_biases(sb, t1, t2, t3, w4, m1, m2, m3, tid, kThreads);
     __syncthreads();
 
     // plain fragments (parts 0, 1) and transposed ones (parts 2, 3); both orientations of a layer hold the
     // same number of fragments, so one set of layer bases serves both
     auto afrag = [&](int f, int part) -> bf16x8 { return frags[(unsigned)((part * P.nfrag + f) * 64 + lane)]; };
-    const int fb1 = 0, fb2 = m1 * 2 * kf, fb3 = fb2 + m2 * 2 * m1;
+    const int fb2 = m1 * 2 * kf, fb3 = fb2 + m2 * 2 * m1;           // layer 1: 0
 
     f32x16 gw1[S1], gw2[S2], gw3[S3];
 #pragma unroll
@@ -282,35 +181,11 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
         const unsigned half_off = (unsigned)(4 * hh * n);
         const unsigned off1 = (half_off + (unsigned)pc) * 4u;
 
-        // layer-1 accumulators of the f1 half, plus t1: once per strip (as the forward)
+        // layer-1 accumulators of the f1 half, plus t1: once per strip
         f32x16 base[M1];
         bf16x8 x1h[KF], x1l[KF];
-#pragma unroll
-        for (int ks = 0; ks < KF; ++ks) {
-            if (EXACT || ks < kf) {
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = ld_off(f1b + (size_t)frag_k_uniform(ks, j) * n, off1);
-                split8(v, x1h[ks], x1l[ks]);
-            }
-        }
-#pragma unroll
-        for (int mo = 0; mo < M1; ++mo) {
-            if (EXACT || mo < m1) {
-                __builtin_amdgcn_sched_barrier(0);
-                f32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = sb[32 * mo + acc_row(i, hh)];
-#pragma unroll
-                for (int ks = 0; ks < KF; ++ks) {
-                    if (EXACT || ks < kf) {
-                        const int f = fb1 + mo * 2 * kf + ks;
-                        mma3(acc, afrag(f, 0), afrag(f, 1), x1h[ks], x1l[ks]);
-                    }
-                }
-                base[mo] = acc;
-            }
-        }
+        f1_frags<3, EXACT, KF>(f1b, n, off1, kf, x1h, x1l);
+        layer1_base<3, EXACT, KF, M1>(base, afrag, sb, kf, m1, hh, x1h, x1l);
 
         f32x16 g1acc[G1];            // dx rows of the f1 half, summed over this wave's displacements
 #pragma unroll
@@ -323,83 +198,16 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
             const int a = disp / d, bb = disp - a * d;
             const float px = (cx + (float)(a - P.radius)) * P.sx;
             const float py = (cy + (float)(bb - P.radius)) * P.sy;
-            const Taps t = match_taps(px, py, P.h, P.w, false);
-            unsigned off2[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) off2[k] = (half_off + (unsigned)t.idx[k]) * 4u;
+            const Taps t = make_taps_fwd(px, py, P.h, P.w);
             const float g = live ? gcost[((size_t)b * dd + disp) * n + pc] : 0.f;
             gb4 += hh == 0 ? g : 0.f;       // both lane halves hold the sample's g
 
-            // ---- forward, as dicl_match_kernel<3>, keeping the masks ----
-            bf16x8 xh[KF], xl[KF];
-#pragma unroll
-            for (int ks = 0; ks < KF; ++ks) {
-                if (EXACT || ks < kf) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float* fc = f2b + (size_t)frag_k_uniform(ks, j) * n;
-                        v[j] = t.wgt[0] * ld_off(fc, off2[0]) + t.wgt[1] * ld_off(fc, off2[1]) +
-                               t.wgt[2] * ld_off(fc, off2[2]) + t.wgt[3] * ld_off(fc, off2[3]);
-                    }
-                    split8(v, xh[ks], xl[ks]);
-                }
-            }
+            // ---- forward, dicl_match_kernel<3>'s, keeping the masks ----
+            bf16x8 xh[KF], xl[KF], yh[2 * M1], yl[2 * M1], zh[2 * M2], zl[2 * M2];
             unsigned mask1[M1], mask2[M2];
-            bf16x8 yh[2 * M1], yl[2 * M1];
-#pragma unroll
-            for (int mo = 0; mo < M1; ++mo) {
-                if (EXACT || mo < m1) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    f32x16 acc = base[mo];
-#pragma unroll
-                    for (int ks = 0; ks < KF; ++ks) {
-                        if (EXACT || ks < kf) {
-                            const int f = fb1 + mo * 2 * kf + kf + ks;
-                            mma3(acc, afrag(f, 0), afrag(f, 1), xh[ks], xl[ks]);
-                        }
-                    }
-                    unsigned m = 0;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) m |= (acc[i] > 0.f ? 1u : 0u) << i;
-                    mask1[mo] = m;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = relu_nan(acc[8 * s + j]);
-                        split8(v, yh[2 * mo + s], yl[2 * mo + s]);
-                    }
-                }
-            }
-            bf16x8 zh[2 * M2], zl[2 * M2];
-#pragma unroll
-            for (int mo = 0; mo < M2; ++mo) {
-                if (EXACT || mo < m2) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    f32x16 acc = {};
-#pragma unroll
-                    for (int ks = 0; ks < 2 * M1; ++ks) {
-                        if (EXACT || ks < 2 * m1) {
-                            const int f = fb2 + mo * 2 * m1 + ks;
-                            mma3(acc, afrag(f, 0), afrag(f, 1), yh[ks], yl[ks]);
-                        }
-                    }
-                    unsigned m = 0;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float z = acc[8 * s + j] + sb[kMaxWidth + 32 * mo + acc_row(8 * s + j, hh)];
-                            m |= (z > 0.f ? 1u : 0u) << (8 * s + j);
-                            v[j] = relu_nan(z);
-                        }
-                        split8(v, zh[2 * mo + s], zl[2 * mo + s]);
-                    }
-                    mask2[mo] = m;
-                }
-            }
+            f2_frags<3, EXACT, KF>(f2b, n, half_off, t, kf, xh, xl);
+            layer1<3, EXACT, true, KF, M1>(base, afrag, kf, m1, hh, xh, xl, yh, yl, mask1);
+            layer2<3, EXACT, true, M1, M2>(afrag, sb, fb2, m1, m2, hh, yh, yl, zh, zl, mask2);
             // layer 3: dz3 = (z3 > 0) ? w4 g : 0, gw4 += a3 g, gt3 += dz3
             bf16x8 d3h[2 * M3], d3l[2 * M3];
 #pragma unroll
@@ -407,13 +215,7 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
                 if (EXACT || mo < m3) {
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16 acc = {};
-#pragma unroll
-                    for (int ks = 0; ks < 2 * M2; ++ks) {
-                        if (EXACT || ks < 2 * m2) {
-                            const int f = fb3 + mo * 2 * m2 + ks;
-                            mma3(acc, afrag(f, 0), afrag(f, 1), zh[ks], zl[ks]);
-                        }
-                    }
+                    mma_tile<3, EXACT, 2 * M2>(acc, afrag, fb3 + mo * 2 * m2, 0, 2 * m2, zh, zl);
                     float dz[16], ag[16];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
@@ -426,8 +228,8 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
                         gw4[mo] += tile_rowsum(ag, red, lane);
                         gt3[mo] += tile_rowsum(dz, red, lane);
                     }
-                    split8(dz, d3h[2 * mo], d3l[2 * mo]);
-                    split8(dz + 8, d3h[2 * mo + 1], d3l[2 * mo + 1]);
+                    split8<3>(dz, d3h[2 * mo], d3l[2 * mo]);
+                    split8<3>(dz + 8, d3h[2 * mo + 1], d3l[2 * mo + 1]);
                 }
             }
 
@@ -451,19 +253,13 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
                 if (EXACT || mo < m2) {
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16 acc = {};
-#pragma unroll
-                    for (int ks = 0; ks < 2 * M3; ++ks) {
-                        if (EXACT || ks < 2 * m3) {
-                            const int f = fb3 + mo * 2 * m3 + ks;
-                            mma3(acc, afrag(f, 2), afrag(f, 3), d3h[ks], d3l[ks]);
-                        }
-                    }
+                    mma_tile<3, EXACT, 2 * M3>(acc, afrag, fb3 + mo * 2 * m3, 2, 2 * m3, d3h, d3l);
                     float dz[16];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) dz[i] = ((mask2[mo] >> i) & 1u) ? acc[i] : 0.f;
                     if (params) gt2[mo] += tile_rowsum(dz, red, lane);
-                    split8(dz, d2h[2 * mo], d2l[2 * mo]);
-                    split8(dz + 8, d2h[2 * mo + 1], d2l[2 * mo + 1]);
+                    split8<3>(dz, d2h[2 * mo], d2l[2 * mo]);
+                    split8<3>(dz + 8, d2h[2 * mo + 1], d2l[2 * mo + 1]);
                 }
             }
 
@@ -487,19 +283,13 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
                 if (EXACT || mo < m1) {
                     __builtin_amdgcn_sched_barrier(0);
                     f32x16 acc = {};
-#pragma unroll
-                    for (int ks = 0; ks < 2 * M2; ++ks) {
-                        if (EXACT || ks < 2 * m2) {
-                            const int f = fb2 + mo * 2 * m2 + ks;
-                            mma3(acc, afrag(f, 2), afrag(f, 3), d2h[ks], d2l[ks]);
-                        }
-                    }
+                    mma_tile<3, EXACT, 2 * M2>(acc, afrag, fb2 + mo * 2 * m2, 2, 2 * m2, d2h, d2l);
                     float dz[16];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) dz[i] = ((mask1[mo] >> i) & 1u) ? acc[i] : 0.f;
                     if (params) gt1[mo] += tile_rowsum(dz, red, lane);
-                    split8(dz, d1h[2 * mo], d1l[2 * mo]);
-                    split8(dz + 8, d1h[2 * mo + 1], d1l[2 * mo + 1]);
+                    split8<3>(dz, d1h[2 * mo], d1l[2 * mo]);
+                    split8<3>(dz + 8, d1h[2 * mo + 1], d1l[2 * mo + 1]);
                 }
             }
 
@@ -522,20 +312,14 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
 
             // ---- dx = W1^T dz1: rows < C to grad_fmap1 (registers), the others scattered to grad_fmap2 ----
             if (gf1 != nullptr || gf2 != nullptr) {
-                const Taps tb = match_taps(px, py, P.h, P.w, true);
+                const Taps tb = make_taps(px, py, P.h, P.w);
                 float* g2b = gf2 != nullptr ? gf2 + (size_t)b * P.C * n : nullptr;
 #pragma unroll
                 for (int mo = 0; mo < KF; ++mo) {
                     if (EXACT || mo < kf) {
                         __builtin_amdgcn_sched_barrier(0);
                         f32x16 acc = {};
-#pragma unroll
-                        for (int ks = 0; ks < 2 * M1; ++ks) {
-                            if (EXACT || ks < 2 * m1) {
-                                const int f = fb1 + mo * 2 * m1 + ks;
-                                mma3(acc, afrag(f, 2), afrag(f, 3), d1h[ks], d1l[ks]);
-                            }
-                        }
+                        mma_tile<3, EXACT, 2 * M1>(acc, afrag, mo * 2 * m1, 2, 2 * m1, d1h, d1l);
                         if (mo < G1) {
 #pragma unroll
                             for (int i = 0; i < 16; ++i) g1acc[mo < G1 ? mo : 0][i] += live ? acc[i] : 0.f;
@@ -635,17 +419,6 @@ dicl_match_grad_reduce_kernel(const float* __restrict__ partw, const float* __re
     }
 }
 
-bool width_ok(int c) { return c >= 32 && c <= kMaxWidth && c % 32 == 0; }
-
-bool grad_supported(int channels, int c1, int c2, int c3, int radius) {
-    return channels >= 16 && channels % 16 == 0 && 2 * channels <= kMaxWidth && width_ok(c1) && width_ok(c2) &&
-           width_ok(c3) && radius >= 1 && radius <= 4;
-}
-
-int grad_nfrag(int channels, int c1, int c2, int c3) {
-    return (c1 / 32) * (2 * channels / 16) + (c2 / 32) * (c1 / 16) + (c3 / 32) * (c2 / 16);
-}
-
 int grad_grid(int batch, long long n) { return (int)std::min<long long>((long long)batch * ((n + 31) / 32), kCUs); }
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -657,7 +430,7 @@ struct Layout {
 
 Layout grad_layout(int batch, int channels, long long n, int c1, int c2, int c3) {
     Layout L;
-    L.frag_bytes = (size_t)4 * grad_nfrag(channels, c1, c2, c3) * 64 * sizeof(bf16x8);
+    L.frag_bytes = (size_t)4 * match_nfrag(channels, c1, c2, c3) * 64 * sizeof(bf16x8);
     L.nw = c1 * 2 * channels + c2 * c1 + c3 * c2;
     L.nv = 2 * c3 + c1 + c2 + 1;
     const size_t grid = (size_t)grad_grid(batch, n);
@@ -673,12 +446,12 @@ Layout grad_layout(int batch, int channels, long long n, int c1, int c2, int c3)
 using namespace rmd;
 
 extern "C" int rmd_dicl_match_1x1_backward_supported(int channels, int c1, int c2, int c3, int radius) {
-    return grad_supported(channels, c1, c2, c3, radius) ? 1 : 0;
+    return match_supported(channels, c1, c2, c3, radius) ? 1 : 0;
 }
 
 extern "C" size_t rmd_dicl_match_1x1_backward_workspace_bytes(int batch, int channels, int height, int width,
                                                               int radius, int c1, int c2, int c3) {
-    if (!grad_supported(channels, c1, c2, c3, radius) || batch <= 0 || height <= 0 || width <= 0) return 0;
+    if (!match_supported(channels, c1, c2, c3, radius) || batch <= 0 || height <= 0 || width <= 0) return 0;
     return grad_layout(batch, channels, (long long)height * width, c1, c2, c3).total;
 }
 
@@ -700,25 +473,16 @@ extern "C" int rmd_dicl_match_1x1_backward(const float* grad_cost, const float* 
     RMD_REQUIRE(ngiven == 0 || ngiven == 8, RMD_ERR_ARG,
                 "rmd_dicl_match_1x1_backward: the eight parameter-gradient pointers are all given or all NULL (%d given)",
                 ngiven);
-    RMD_REQUIRE(batch > 0 && height > 0 && width > 0, RMD_ERR_SHAPE, "rmd_dicl_match_1x1_backward: bad sizes");
-    RMD_REQUIRE(grad_supported(channels, c1, c2, c3, radius), RMD_ERR_SHAPE,
-                "rmd_dicl_match_1x1_backward: unsupported (channels=%d widths=%d,%d,%d radius=%d): channels a "
-                "multiple of 16 up to 64, widths multiples of 32 up to 128, radius 1..4", channels, c1, c2, c3, radius);
+    if (int rc = match_check_shape("rmd_dicl_match_1x1_backward", batch, channels, height, width, radius, c1, c2, c3))
+        return rc;
     const long long n = (long long)height * width;
-    RMD_REQUIRE(n * channels < (1ll << 30), RMD_ERR_SHAPE,
-                "rmd_dicl_match_1x1_backward: %lld pixels x %d channels per image", n, channels);
     if (ngiven == 0 && !grad_fmap1 && !grad_fmap2) return RMD_OK;
 
     GradParams P;
-    P.B = batch; P.C = channels; P.n = (int)n; P.h = height; P.w = width; P.radius = radius;
-    P.kf = channels / 16; P.m1 = c1 / 32; P.m2 = c2 / 32; P.m3 = c3 / 32;
-    P.nfrag = grad_nfrag(channels, c1, c2, c3);
-    P.nstrips = (int)((n + 31) / 32);
+    static_cast<MatchGeom&>(P) = match_geom(batch, channels, height, width, radius, c1, c2, c3);
     const Layout L = grad_layout(batch, channels, n, c1, c2, c3);
     P.nw = L.nw; P.nv = L.nv;
     P.params = ngiven == 8;
-    P.sx = (float)(width - 1) / (float)(width - 1);
-    P.sy = (float)(height - 1) / (float)(height - 1);
     const int grid = grad_grid(batch, n);
     hipStream_t st = as_stream(stream);
     unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
@@ -726,37 +490,19 @@ extern "C" int rmd_dicl_match_1x1_backward(const float* grad_cost, const float* 
     float* partw = reinterpret_cast<float*>(ws + L.partw_off);
     float* partv = reinterpret_cast<float*>(ws + L.partv_off);
 
-    PackDesc D;
-    const float* src[3] = {w1, w2, w3};
-    const int cin[3] = {2 * channels, c1, c2}, cout[3] = {c1, c2, c3};
-    int first = 0;
-    for (int o = 0; o < 2; ++o) {
-        for (int l = 0; l < 3; ++l) {
-            const int m = 3 * o + l;
-            D.src[m] = src[l];
-            D.row_stride[m] = o == 0 ? cin[l] : 1;          // plain: A = W_l; transposed: A[row][k] = W_l[k][row]
-            D.k_stride[m] = o == 0 ? 1 : cin[l];
-            D.ksteps[m] = (o == 0 ? cin[l] : cout[l]) / 16;
-            D.first[m] = first;
-            first += (cout[l] / 32) * (cin[l] / 16);
-        }
-    }
-    D.first[6] = first;
-    dicl_match_grad_pack_kernel<<<(2 * P.nfrag * 64 + 255) / 256, 256, 0, st>>>(D, P.nfrag, frags);
+    // plain fragments for the recomputed forward, transposed ones for the data backward
+    match_pack<2>(match_pack_desc(w1, w2, w3, channels, c1, c2, c3, 2), P.nfrag, true, frags, st);
     if (grad_fmap2) (void)hipMemsetAsync(grad_fmap2, 0, sizeof(float) * (size_t)batch * channels * n, st);
 
-#define RMD_MATCH_GRAD(EX, KF, M1, M2, M3)                                                                     \
-    do {                                                                                                        \
-        auto k = dicl_match_grad_kernel<EX, KF, M1, M2, M3>;                                                    \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  kLdsBytes);                                                                  \
-        k<<<grid, kThreads, kLdsBytes, st>>>(grad_cost, fmap1, fmap2, coords, frags, t1, t2, t3, w4, P,         \
-                                             grad_fmap1, grad_fmap2, partw, partv);                             \
-    } while (0)
-    // as the forward: the reference's two configurations have loops of their own size
-    if (P.kf == 2 && P.m1 == 3 && P.m2 == 4 && P.m3 == 2) RMD_MATCH_GRAD(true, 2, 3, 4, 2);
-    else if (P.kf <= 2 && P.m1 <= 2 && P.m2 <= 2 && P.m3 <= 1) RMD_MATCH_GRAD(false, 2, 2, 2, 1);
-    else RMD_MATCH_GRAD(false, 4, 4, 4, 4);
+#define RMD_MATCH_GRAD(EX, KF, M1, M2, M3)                                                                        \
+    launch_lds(dicl_match_grad_kernel<EX, KF, M1, M2, M3>, grid, kThreads, kLdsBytes, st, grad_cost, fmap1, fmap2, \
+               coords, frags, t1, t2, t3, w4, P, grad_fmap1, grad_fmap2, partw, partv)
+    // the forward's classes: the two kernels cannot disagree on which instance a shape gets
+    switch (match_class(P)) {
+    case MatchClass::kExact2342: RMD_MATCH_GRAD(true, 2, 3, 4, 2); break;
+    case MatchClass::kGuarded2221: RMD_MATCH_GRAD(false, 2, 2, 2, 1); break;
+    case MatchClass::kGuarded4444: RMD_MATCH_GRAD(false, 4, 4, 4, 4); break;
+    }
 #undef RMD_MATCH_GRAD
     if (P.params) {
         ReduceOut O;
