@@ -687,6 +687,43 @@ int rmd_dicl_match_1x1_backward(const float* grad_cost, const float* fmap1, cons
                                 float* grad_w3, float* grad_t3, float* grad_w4, float* grad_b4, void* workspace,
                                 void* stream);
 
+/*
+ * Fused SepConvGRU, inference only: SepConvGru.forward (src/models/impls/raft.py:228-259).  h (B, Hd, H, W),
+ * x (B, Xd, H, W), out (B, Hd, H, W), all float32.  One half-step along one axis (axis 0: 1x5 along W with
+ * padding (0, 2); axis 1: 5x1 along H with padding (2, 0)) is
+ *   hx = [h ; x]    z = sigmoid(Wz * hx + bz)    r = sigmoid(Wr * hx + br)
+ *   q = tanh(Wq * [r.h ; x] + bq)                h' = (1 - z) h + z q
+ * where * is F.conv2d's cross-correlation (tap t reads position p + t - 2, zero outside the map).
+ * rmd_sepconv_gru (raft.py:228-259) runs both halves: weights / biases are host arrays of six device
+ * pointers in the order z1, r1, q1 (each (Hd, Hd + Xd, 1, 5)), z2, r2, q2 (each (Hd, Hd + Xd, 5, 1)), biases
+ * Hd floats each.  rmd_sepconv_gru_half (raft.py:240-247 for axis 0, 249-256 for axis 1) runs one half with
+ * three weights and biases (z, r, q).  Every convolution is an MFMA implicit GEMM whose operands pass
+ * through bfloat16:
+ *   compute = RMD_BF16X3 : three split-bf16 products (hi.hi + hi.lo + lo.hi), fp32 accumulation — the
+ *                          parity mode
+ *   compute = RMD_BF16   : one bf16 product
+ * Biases, sigmoid, tanh and the gating are fp32 in both.  A NaN input gives NaN in exactly the outputs
+ * whose receptive field holds it; a +-inf input gives NaN there in the parity mode (inf - inf in the
+ * residual), the one deviation from the reference.  Supported (rmd_sepconv_gru_supported, host only;
+ * RMD_ERR_SHAPE otherwise): Hd a multiple of 32 in 32..128, Xd a multiple of 16, Hd + Xd <= 512,
+ * (Hd + Xd) H W < 2^30, any B, H, W >= 1.  `out` must not overlap `h` or `x` (RMD_ERR_ARG).  `workspace`
+ * holds rmd_sepconv_gru_workspace_bytes() bytes (0 = unsupported arguments) = the packed weights
+ * (6 Hd 5 (Hd + Xd) elements x 2 parts x 2 bytes) + three (B, Hd, H, W) fp32 maps (z, r.h, and the h
+ * between the halves) + 1024: the call first repacks the weights into it as MFMA A fragments, so it may be
+ * reused by the next call on the same stream.  Nothing else is written to memory: no cat, no unfolded
+ * tensor, no pre-activation.  The summation order is fixed and a sample's result does not depend on the
+ * rest of the batch: bitwise reproducible.  The launcher never allocates, frees or synchronises, reads no
+ * environment variable, and all argument checks run before any launch.
+ */
+int rmd_sepconv_gru_supported(int hidden, int input);
+size_t rmd_sepconv_gru_workspace_bytes(int batch, int hidden, int input, int height, int width);
+int rmd_sepconv_gru(const float* h, const float* x, const float* const* weights, const float* const* biases,
+                    float* out, void* workspace, int batch, int hidden, int input, int height, int width,
+                    int compute, void* stream);
+int rmd_sepconv_gru_half(const float* h, const float* x, const float* const* weights, const float* const* biases,
+                         float* out, void* workspace, int batch, int hidden, int input, int height, int width,
+                         int axis, int compute, void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

@@ -121,6 +121,10 @@ _SIGS = {
     "rmd_dicl_match_1x1_backward_supported": (_I, [_I] * 5),
     "rmd_dicl_match_1x1_backward_workspace_bytes": (ctypes.c_size_t, [_I] * 8),
     "rmd_dicl_match_1x1_backward": (_I, [_P] * 4 + [_I] * 5 + [_P] * 7 + [_I] * 4 + [_P] * 12),
+    "rmd_sepconv_gru_supported": (_I, [_I] * 2),
+    "rmd_sepconv_gru_workspace_bytes": (ctypes.c_size_t, [_I] * 5),
+    "rmd_sepconv_gru": (_I, [_P] * 6 + [_I] * 6 + [_P]),
+    "rmd_sepconv_gru_half": (_I, [_P] * 6 + [_I] * 7 + [_P]),
     "rmd_local_cross_attn_kernel":(ctypes.c_char_p, [_I] * 9),
     "rmd_local_cross_attn": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P]),
     "rmd_local_cross_attn_workspace_bytes": (ctypes.c_size_t, [_I] * 5),

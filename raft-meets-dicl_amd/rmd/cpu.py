@@ -23,8 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_head_args, check_loss_args, check_match_args,
-                      check_match_backward_args, check_metric_args,
+from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_gru_args, check_head_args, check_loss_args,
+                      check_match_args, check_match_backward_args, check_metric_args,
                       pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
@@ -584,6 +584,23 @@ def dicl_match_1x1_backward(grad, fmap1, fmap2, coords, radius, weights, biases,
     return [next(got) if need else t.new_empty((0,)) for t, need in zip(ins, needs)]
 
 
+# ---- fused SepConvGRU (raft.py:228-259) -------------------------------------------------------------
+
+def sepconv_gru(h, x, weights, biases, compute):
+    """The reference's own composition, fp32 whatever the compute mode: the horizontal half (1x5, padding
+    (0, 2)), then the vertical one (5x1, padding (2, 0))."""
+    check_gru_args(h, x, weights, biases, compute)
+    h, x = h.detach().float(), x.detach().float()
+    ws, bs = [t.detach().float() for t in weights], [t.detach().float().reshape(-1) for t in biases]
+    for i, pad in ((0, (0, 2)), (3, (2, 0))):
+        hx = torch.cat([h, x], dim=1)
+        z = torch.sigmoid(F.conv2d(hx, ws[i], bs[i], padding=pad))
+        r = torch.sigmoid(F.conv2d(hx, ws[i + 1], bs[i + 1], padding=pad))
+        q = torch.tanh(F.conv2d(torch.cat((r * h, x), dim=1), ws[i + 2], bs[i + 2], padding=pad))
+        h = (1.0 - z) * h + z * q
+    return h
+
+
 # ---- registration ------------------------------------------------------------------------------
 #
 # The CPU kernel of an operator is the function of its name in this module.
@@ -593,5 +610,5 @@ assert all(_KERNELS.values()), f"every rmd operator needs a CPU kernel: {[n for 
 
 for _name, _fn in _KERNELS.items():
     LIB.impl(_name, _fn, "CPU")
-    if _name not in ("flow_metrics", "dicl_match_1x1"):     # not differentiable: library.py's Autograd kernel serves every device
+    if _name not in ("flow_metrics", "dicl_match_1x1", "sepconv_gru"):     # not differentiable: library.py's Autograd kernel serves every device
         LIB.impl(_name, _fn, "AutogradCPU")

@@ -28,6 +28,7 @@ follow SURVEY.md §8(b):
         compute) -> (B, 2r+1, 2r+1, h, w) cost
   dicl_match_1x1_train(fmap1, fmap2, coords, radius, weights[], biases[])    the same cost (fp32 mode), differentiable:
         / dicl_match_1x1_backward(grad, ..., needs_grad) -> grads[]          its formula recomputes from the inputs
+  sepconv_gru(h, x, weights[], biases[], compute) -> (B, Hd, H, W)           raft.py:228-259 (inference)
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -45,9 +46,9 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head", "attn", "match" and "match_train" are listed by
-# loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators() and
-# match_train_operators().
+# set (operators()); "loss", "metric", "head", "attn", "match", "match_train" and "update" are listed by
+# loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
+# match_train_operators() and update_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -92,6 +93,7 @@ _OPS = {
                                             "Tensor[] weights, Tensor[] biases) -> Tensor"),
     "dicl_match_1x1_backward": ("match_train", "(Tensor grad, Tensor fmap1, Tensor fmap2, Tensor coords, int radius, "
                                                "Tensor[] weights, Tensor[] biases, bool[] needs_grad) -> Tensor[]"),
+    "sepconv_gru": ("update", "(Tensor h, Tensor x, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
 }
 for _name, (_, _schema) in _OPS.items():
     LIB.define(_name + _schema)
@@ -134,6 +136,11 @@ def match_operators():
 def match_train_operators():
     """Names of the registered torch.ops.rmd differentiable fused matching-network operators."""
     return _family("match_train")
+
+
+def update_operators():
+    """Names of the registered torch.ops.rmd update-block (recurrent unit) operators."""
+    return _family("update")
 
 
 def _hip(name):
@@ -1274,3 +1281,78 @@ def _match_train_bwd(ctx, grad):
 
 
 torch.library.register_autograd("rmd::dicl_match_1x1_train", _match_train_bwd, setup_context=_match_train_setup)
+
+
+# ---- fused SepConvGRU (raft.py:228-259), inference --------------------------------------------------
+#
+# weights = [z1, r1, q1 (Hd, Hd + Xd, 1, 5), z2, r2, q2 (Hd, Hd + Xd, 5, 1)], biases = six (Hd,) vectors: the
+# parameters of SepConvGru in the order its forward uses them.  Not differentiable: like dicl_match_1x1, its
+# Autograd kernel runs the backend kernel below autograd (training keeps the module's eager path).
+
+GRU_COMPUTE = (_lib.RMD_BF16X3, _lib.RMD_BF16)
+
+
+def check_gru_args(h, x, weights, biases, compute):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of sepconv_gru; returns
+    (hidden, input) widths."""
+    if h.dim() != 4 or x.dim() != 4 or h.shape[0] != x.shape[0] or h.shape[2:] != x.shape[2:]:
+        raise ValueError(f"sepconv_gru: h (B, Hd, H, W) and x (B, Xd, H, W) expected, got {tuple(h.shape)} / "
+                         f"{tuple(x.shape)}")
+    if min(h.shape) < 1 or x.shape[1] < 1:
+        raise ValueError(f"sepconv_gru: empty h {tuple(h.shape)} or x {tuple(x.shape)}")
+    if len(weights) != 6 or len(biases) != 6:
+        raise ValueError(f"sepconv_gru: need 6 weights and 6 biases, got {len(weights)} and {len(biases)}")
+    if compute not in GRU_COMPUTE:
+        raise ValueError(f"sepconv_gru: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    hd, xd = h.shape[1], x.shape[1]
+    for i, (wt, bs) in enumerate(zip(weights, biases)):
+        want = (hd, hd + xd, 1, 5) if i < 3 else (hd, hd + xd, 5, 1)
+        if tuple(wt.shape) != want:
+            raise ValueError(f"sepconv_gru: weights[{i}] must be {want}, got {tuple(wt.shape)}")
+        if bs.numel() != hd:
+            raise ValueError(f"sepconv_gru: biases[{i}] must hold {hd} elements, got {tuple(bs.shape)}")
+    for t in (h, x, *weights, *biases):
+        if not t.is_floating_point():
+            raise ValueError(f"sepconv_gru: tensors must be floating point, got {t.dtype}")
+    return hd, xd
+
+
+def gru_supported(hidden, input):
+    """rmd_sepconv_gru_supported: whether the HIP kernel serves these widths (host only)."""
+    return bool(_lib.lib().rmd_sepconv_gru_supported(hidden, input))
+
+
+GRU_MAX_IMAGE = 1 << 30     # (Hd + Xd) H W per image: 32-bit lane offsets inside an image
+
+
+def _pointers(tensors):
+    return (ctypes.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
+
+
+@_hip("sepconv_gru")
+def _sepconv_gru(h, x, weights, biases, compute):
+    hd, xd = check_gru_args(h, x, weights, biases, compute)
+    b, _, ht, wd = h.shape
+    if not gru_supported(hd, xd) or (hd + xd) * ht * wd >= GRU_MAX_IMAGE:
+        raise ValueError(f"sepconv_gru: unsupported on the GPU: hidden {hd} (a multiple of 32 in 32..128), input {xd} "
+                         f"(a multiple of 16), hidden + input <= 512, (hidden + input) H W < 2^30")
+    hh, xx = _f32(h), _f32(x)
+    ws, ts = [_f32(t) for t in weights], [_f32(t) for t in biases]
+    work = _lib.workspace("sepconv_gru", hh, b, hd, xd, ht, wd)
+    out = _like(hh)
+    _lib.launch("rmd_sepconv_gru", hh, hh, xx, _pointers(ws), _pointers(ts), out, work, b, hd, xd, ht, wd, compute)
+    return out
+
+
+@_fake("sepconv_gru")
+def _(h, x, weights, biases, compute):
+    check_gru_args(h, x, weights, biases, compute)
+    return _like(h)
+
+
+def _sepconv_gru_below_autograd(h, x, weights, biases, compute):
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.rmd.sepconv_gru(h, x, weights, biases, compute)
+
+
+LIB.impl("sepconv_gru", _sepconv_gru_below_autograd, "Autograd")

@@ -483,6 +483,20 @@ def dicl_match_1x1(fmap1, fmap2, coords, radius, weights, biases, precision="fp3
     return torch.ops.rmd.dicl_match_1x1(fmap1, fmap2, coords, int(radius), weights, biases, MATCH_PRECISIONS[precision])
 
 
+GRU_PRECISIONS = MATCH_PRECISIONS
+
+
+def sepconv_gru(h, x, weights, biases, precision="fp32"):
+    """Fused SepConvGRU (torch.ops.rmd.sepconv_gru; raft.py:228-259), inference only: h (B, Hd, H, W),
+    x (B, Xd, H, W), weights [z1, r1, q1, z2, r2, q2] and their biases -> the new h.  precision "fp32": three
+    split-bf16 products per convolution (parity mode); "bf16": one.  Not differentiable."""
+    if precision not in GRU_PRECISIONS:
+        raise ValueError(f"sepconv_gru: unknown precision '{precision}', expected one of {sorted(GRU_PRECISIONS)}")
+    weights, biases = list(weights), list(biases)
+    _same_device(h, x, *weights, *biases)
+    return torch.ops.rmd.sepconv_gru(h, x, weights, biases, GRU_PRECISIONS[precision])
+
+
 def dicl_stack_int(fmap1, fmap2, ru, rv):
     """Integer-displacement matching volume with occlusion mask (torch.ops.rmd.dicl_stack_int;
     impls/dicl.py:212-238)."""

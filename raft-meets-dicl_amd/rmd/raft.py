@@ -78,3 +78,5 @@ class CorrBlock:
 # per-iteration heads of raft.py (Up8Network :299-331, soft-argmax regressions :98-190)
 from .heads import (Up8Network, SoftArgMaxFlowRegression, SoftArgMaxFlowRegressionWithDap,  # noqa: E402,F401
                     make_flow_regression)
+# the update block of raft.py (:193-296), its recurrent unit optionally the fused HIP operator
+from .update import BasicMotionEncoder, SepConvGru, FlowHead, BasicUpdateBlock  # noqa: E402,F401

@@ -1,0 +1,167 @@
+"""Drop-ins for RAFT's update block — qzed/raft-meets-dicl src/models/impls/raft.py:193-296.
+
+BasicMotionEncoder, SepConvGru, FlowHead and BasicUpdateBlock with the reference's constructor arguments,
+attribute names and state-dict keys.  The encoder and the flow head are the reference's plain torch
+modules.  SepConvGru keeps the reference's composition as its default (``fused="off"``) and, in inference,
+can run the whole unit as the fused HIP operator torch.ops.rmd.sepconv_gru (csrc/gru.hip): six MFMA
+implicit-GEMM convolutions with the sigmoid / tanh / gating in their epilogues, no cat, no pre-activation
+in memory.
+
+``fused``:
+  "off"   the reference's composition line for line (bitwise the reference's on the CPU); trains.
+  "auto"  the operator iff the tensors are fp32 GPU tensors, autocast is off, no gradient is needed (grad
+          mode off, or neither h, x nor a parameter requires grad) and the widths are supported; the
+          composition otherwise.  CPU tensors run the operator's CPU kernel under the same conditions.
+  "on"    as "auto", but a RuntimeError naming the reason where "auto" would fall back.
+``precision`` is the operator's: "fp32" (three split-bf16 products, the parity mode) or "bf16" (one).
+
+Forward hooks on the six inner convolutions do not fire on the fused path (they are never called); hooks on
+the unit itself and on the update block do.
+"""
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import library, ops
+
+FUSED_MODES = ("off", "auto", "on")
+
+
+class BasicMotionEncoder(nn.Module):
+    """Encoder to combine correlation and flow for GRU input (raft.py:193-225)"""
+
+    def __init__(self, corr_planes):
+        super().__init__()
+
+        self.convc1 = nn.Conv2d(corr_planes, 256, 1, padding=0)
+        self.convc2 = nn.Conv2d(256, 192, 3, padding=1)
+
+        self.convf1 = nn.Conv2d(2, 128, 7, padding=3)
+        self.convf2 = nn.Conv2d(128, 64, 3, padding=1)
+
+        self.conv = nn.Conv2d(192 + 64, 128 - 2, 3, padding=1)
+
+        self.output_dim = 128                           # (128 - 2) + 2
+
+    def forward(self, flow, corr):
+        cor = F.relu(self.convc1(corr))
+        cor = F.relu(self.convc2(cor))
+
+        flo = F.relu(self.convf1(flow))
+        flo = F.relu(self.convf2(flo))
+
+        combined = torch.cat([cor, flo], dim=1)
+        combined = F.relu(self.conv(combined))
+
+        return torch.cat([combined, flow], dim=1)
+
+
+class SepConvGru(nn.Module):
+    """Convolutional 2-part (horizontal/vertical) GRU for flow updates (raft.py:228-259)"""
+
+    def __init__(self, hidden_dim=128, input_dim=128+128, fused="off", precision="fp32"):
+        super().__init__()
+        if fused not in FUSED_MODES:
+            raise ValueError(f"SepConvGru: unknown fused mode '{fused}', expected one of {FUSED_MODES}")
+        if precision not in ops.GRU_PRECISIONS:
+            raise ValueError(f"SepConvGru: unknown precision '{precision}', expected one of {sorted(ops.GRU_PRECISIONS)}")
+        self.fused = fused
+        self.precision = precision
+
+        # horizontal GRU
+        self.convz1 = nn.Conv2d(hidden_dim + input_dim, hidden_dim, (1, 5), padding=(0, 2))
+        self.convr1 = nn.Conv2d(hidden_dim + input_dim, hidden_dim, (1, 5), padding=(0, 2))
+        self.convq1 = nn.Conv2d(hidden_dim + input_dim, hidden_dim, (1, 5), padding=(0, 2))
+
+        # vertical GRU
+        self.convz2 = nn.Conv2d(hidden_dim + input_dim, hidden_dim, (5, 1), padding=(2, 0))
+        self.convr2 = nn.Conv2d(hidden_dim + input_dim, hidden_dim, (5, 1), padding=(2, 0))
+        self.convq2 = nn.Conv2d(hidden_dim + input_dim, hidden_dim, (5, 1), padding=(2, 0))
+
+    def _convs(self):
+        return (self.convz1, self.convr1, self.convq1, self.convz2, self.convr2, self.convq2)
+
+    def fallback_reason(self, h, x):
+        """Why the fused operator cannot serve this call (None if it can)."""
+        params = [p for c in self._convs() for p in (c.weight, c.bias)]
+        tensors = [h, x] + params
+        if any(t.device != h.device for t in tensors):
+            return "h, x and the parameters are on different devices"
+        if any(t.dtype != torch.float32 for t in tensors):
+            return "the tensors are not all float32"
+        if torch.is_autocast_enabled() or (h.device.type == "cpu" and torch.is_autocast_enabled("cpu")):
+            return "autocast is on"
+        if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+            return "a gradient is needed (the fused unit is inference only)"
+        if h.dim() != 4 or x.dim() != 4:
+            return f"h and x must be 4-D, got {tuple(h.shape)} / {tuple(x.shape)}"
+        if h.is_cuda:
+            hd, xd = h.shape[1], x.shape[1]
+            if not library.gru_supported(hd, xd):
+                return (f"unsupported widths: hidden {hd} (a multiple of 32 in 32..128), input {xd} (a multiple of "
+                        f"16), hidden + input <= 512")
+            if (hd + xd) * h.shape[2] * h.shape[3] >= library.GRU_MAX_IMAGE:
+                return f"unsupported size: (hidden + input) H W = {(hd + xd) * h.shape[2] * h.shape[3]} >= 2^30"
+        return None
+
+    def forward(self, h, x):
+        if self.fused != "off":
+            reason = self.fallback_reason(h, x)
+            if reason is None:
+                convs = self._convs()
+                return ops.sepconv_gru(h, x, [c.weight for c in convs], [c.bias for c in convs], self.precision)
+            if self.fused == "on":
+                raise RuntimeError(f"SepConvGru(fused='on'): {reason}")
+
+        # horizontal GRU
+        hx = torch.cat([h, x], dim=1)                               # input vector
+        z = torch.sigmoid(self.convz1(hx))                          # update gate vector
+        r = torch.sigmoid(self.convr1(hx))                          # reset gate vector
+        q = torch.tanh(self.convq1(torch.cat((r * h, x), dim=1)))   # candidate activation
+        h = (1.0 - z) * h + z * q                                   # output vector
+
+        # vertical GRU
+        hx = torch.cat([h, x], dim=1)                               # input vector
+        z = torch.sigmoid(self.convz2(hx))                          # update gate vector
+        r = torch.sigmoid(self.convr2(hx))                          # reset gate vector
+        q = torch.tanh(self.convq2(torch.cat((r * h, x), dim=1)))   # candidate activation
+        h = (1.0 - z) * h + z * q                                   # output vector
+
+        return h
+
+
+class FlowHead(nn.Module):
+    """Head to compute delta-flow from GRU hidden-state (raft.py:262-273)"""
+
+    def __init__(self, input_dim=128, hidden_dim=256, relu_inplace=True):
+        super().__init__()
+
+        self.conv1 = nn.Conv2d(input_dim, hidden_dim, 3, padding=1)
+        self.conv2 = nn.Conv2d(hidden_dim, 2, 3, padding=1)
+        self.relu = nn.ReLU(inplace=relu_inplace)
+
+    def forward(self, x):
+        return self.conv2(self.relu(self.conv1(x)))
+
+
+class BasicUpdateBlock(nn.Module):
+    """Network to compute single flow update delta (raft.py:276-296)"""
+
+    def __init__(self, corr_planes, input_dim=128, hidden_dim=128, relu_inplace=True, *, gru_fused="off",
+                 gru_precision="fp32"):
+        super().__init__()
+
+        self.enc = BasicMotionEncoder(corr_planes)
+        self.gru = SepConvGru(hidden_dim=hidden_dim, input_dim=input_dim+self.enc.output_dim, fused=gru_fused,
+                              precision=gru_precision)
+        self.flow = FlowHead(input_dim=hidden_dim, hidden_dim=256, relu_inplace=relu_inplace)
+
+    def forward(self, h, x, corr, flow):
+        m = self.enc(flow, corr)            # motion features
+        x = torch.cat((x, m), dim=1)        # input for GRU
+
+        h = self.gru(h, x)                  # update hidden state (N, hidden, h/8, w/8)
+        d = self.flow(h)                    # compute flow delta from hidden state (N, 2, h/8, w/8)
+
+        return h, d
