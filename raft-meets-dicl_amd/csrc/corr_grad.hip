@@ -11,10 +11,8 @@
 //   2: ((n / 8) * ldb + k) * 8 + n % 8          3: ((k / 8) * ldb + n) * 8 + k % 8
 // (2 / 3 are the 8-target chunked order of the pyramid gradient G, corr_backward.hip)
 // (dP is then un-pooled onto dfmap2 by rmd_corr_unpool_targets).  Both run here in fp32 accuracy
-// as three bf16 MFMA products per k-step, x = hi + lo, hi = bf16(x), lo = bf16(x - hi):
-//   acc += A_lo.B_hi + A_hi.B_lo + A_hi.B_hi        (the dropped lo.lo term is ~2^-16 relative)
-// — the same split as the forward x3 GEMM (corr_pyramid_x3.hip) — instead of hipBLASLt's exact-f32
-// MFMA path (v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate).
+// as the three bf16 MFMA products per k-step of mfma_bf16.h — the same split as the forward x3 GEMM
+// (corr_pyramid_x3.hip) — instead of hipBLASLt's exact-f32 MFMA path.
 //
 // Geometry: one workgroup (8 waves, 2 per SIMD) owns a 256 (M) x 128 (Nc) output tile; wave
 // (wm = w & 3, wn = w >> 2) owns 64 x 64 = 2 x 2 tiles of v_mfma_f32_32x32x16_bf16.  K runs in
@@ -25,14 +23,10 @@
 // over `splits` workgroups when the tile grid alone does not fill the 256 CUs; the partial tiles go to
 // a workspace and a second kernel sums them in a fixed order (deterministic, no atomics).
 
-#include "rmd_common.h"
+#include "mfma_bf16.h"
 
 namespace rmd {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kTM = 256, kKC = 32;
 constexpr int kRowB = 144;                                  // hi 64 B | lo 64 B | pad 16 B (9 x 16 B: odd)
@@ -52,15 +46,10 @@ struct GemmArgs {
     int splits, ntm, ntn;
 };
 
-__device__ __forceinline__ void split4(float a, float b, float c, float d, bf16x4& hi, bf16x4& lo) {
-    hi[0] = (__bf16)a;
-    hi[1] = (__bf16)b;
-    hi[2] = (__bf16)c;
-    hi[3] = (__bf16)d;
-    lo[0] = (__bf16)(a - (float)hi[0]);
-    lo[1] = (__bf16)(b - (float)hi[1]);
-    lo[2] = (__bf16)(c - (float)hi[2]);
-    lo[3] = (__bf16)(d - (float)hi[3]);
+// a float4 as hi / lo bf16, every hi first (mfma_bf16.h: this kernel's schedule depends on that order)
+__device__ __forceinline__ void split4(const float4& r, bf16x4& hi, bf16x4& lo) {
+    const float v[4] = {r.x, r.y, r.z, r.w};
+    split_hi_first(v, hi, lo);
 }
 
 // the 4 consecutive elements k .. k + 3 at `at` (the address of element k; row valid, k < kend
@@ -192,7 +181,7 @@ grad_gemm_x3(GemmArgs p) {
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             bf16x4 hi, lo;
-            split4(ra[it].x, ra[it].y, ra[it].z, ra[it].w, hi, lo);
+            split4(ra[it], hi, lo);
             unsigned char* d = sA + (it * 64 + (tid >> 3)) * kRowB + (tid & 7) * 8;
             *reinterpret_cast<bf16x4*>(d) = hi;
             if constexpr (X3) *reinterpret_cast<bf16x4*>(d + 64) = lo;
@@ -219,9 +208,8 @@ grad_gemm_x3(GemmArgs p) {
                 const float* cols[4] = {c0, c1, c2, c3};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    __bf16 h0 = (__bf16)cols[j][0], h1 = (__bf16)cols[j][1];
-                    __bf16 l0 = (__bf16)(cols[j][0] - (float)h0), l1 = (__bf16)(cols[j][1] - (float)h1);
-                    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+                    const __bf16 h0 = bf16_hi(cols[j][0]), h1 = bf16_hi(cols[j][1]);
+                    const __bf16 l0 = bf16_lo(cols[j][0], h0), l1 = bf16_lo(cols[j][1], h1);
                     unsigned char* d = sB + (nr + j) * kRowB + kq * 4;
                     *reinterpret_cast<bf16x2*>(d) = bf16x2{h0, h1};
                     if constexpr (X3) *reinterpret_cast<bf16x2*>(d + 64) = bf16x2{l0, l1};
@@ -236,7 +224,7 @@ grad_gemm_x3(GemmArgs p) {
                     continue;
                 }
                 bf16x4 hi, lo;
-                split4(rb[it].x, rb[it].y, rb[it].z, rb[it].w, hi, lo);
+                split4(rb[it], hi, lo);
                 unsigned char* d = sB + (it * 64 + (tid >> 3)) * kRowB + (tid & 7) * 8;
                 *reinterpret_cast<bf16x4*>(d) = hi;
                 if constexpr (X3) *reinterpret_cast<bf16x4*>(d + 64) = lo;
@@ -284,19 +272,13 @@ grad_gemm_x3(GemmArgs p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    f32x16 t = acc[i][j];
-                    if constexpr (X3) {
-                        t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], t, 0, 0, 0);
-                        t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], t, 0, 0, 0);
-                    }
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], t, 0, 0, 0);
-                }
+                for (int j = 0; j < NJ; ++j) mma<X3 ? 3 : 1>(acc[i][j], ah[i], al[i], bh[j], bl[j]);
         }
         __syncthreads();                                       // chunk c+1 published; buffer c free
     }
 
-    // C tile (32 x 32): lane (j32, h) holds rows 8 (v >> 2) + 4 h + (v & 3) of column j32
+    // C tile (32 x 32): lane (j32, h) holds rows acc_row(v, h) of column j32 (spelled out: through acc_row the
+    // sum associates differently and the whole kernel schedules differently)
     float* __restrict__ o = p.out + ((size_t)split * p.batch + b) * p.so;
 #pragma unroll
     for (int i = 0; i < 2; ++i)

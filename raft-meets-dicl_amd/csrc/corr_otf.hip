@@ -27,7 +27,7 @@
 // rmd_corr_lookup does (shared bilinear weights, NaN for 1-pixel levels, zeroed masked levels).  A box
 // of more than kMaxTasks segments (flow differing by hundreds of pixels inside one block) takes a
 // per-query VALU patch path.
-#include "rmd_common.h"
+#include "mfma_bf16.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -58,9 +58,6 @@ constexpr LookShape kShapeF32{1, 2, 256, 1, false};  // f32: query fragments in 
 // cfg2 A/B (profiles/otf_put_ab_r04.json): bf16 70.8-73.2 us with true vs 75.9-78.5 with false; split-bf16
 // (two waves per SIMD) 150 with false vs 170 with true; f32 goes with split-bf16
 constexpr bool kPutSelBf16 = true, kPutSelSplit = false;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 template <typename T> struct Seg;
 template <> struct Seg<__bf16> {
@@ -129,7 +126,7 @@ size_t otf_scratch_elems(const OtfGeom& g) {
     return n;
 }
 size_t otf_scratch_offset(const OtfGeom& g, size_t es) {
-    return ((size_t)g.B * (g.QS + g.TS) * 16 * g.Cp * es + 255) / 256 * 256;
+    return align256((size_t)g.B * (g.QS + g.TS) * 16 * g.Cp * es);
 }
 
 // Level l of fmap2 as the reference builds it (raft_fs.py:27-30): F.avg_pool2d(k=2, s=2) of level l-1.
@@ -543,8 +540,6 @@ constexpr int kBwdThreads = 512;
 constexpr int kMaxRec = 16;                          // records per launch (more: several launches)
 constexpr int kFar = -(1 << 29);                     // origin of a masked / degenerate level
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 struct OtfRecords {
     const int2* org[kMaxRec];                       // (L, B, N) patch origins (x0, y0) at level l
     const float* wp[kMaxRec];                       // (L, B, K*K, N) patch weights
@@ -552,10 +547,10 @@ struct OtfRecords {
 };
 
 size_t otf_record_org_bytes(int B, int H, int W, int L) {
-    return ((size_t)L * B * H * W * sizeof(int2) + 255) / 256 * 256;
+    return align256((size_t)L * B * H * W * sizeof(int2));
 }
 size_t otf_record_wp_bytes(int B, int H, int W, int L, int K) {
-    return ((size_t)L * B * H * W * K * K * sizeof(float) + 255) / 256 * 256;
+    return align256((size_t)L * B * H * W * K * K * sizeof(float));
 }
 
 // |v| as ordered integer bits for an atomicMax of finite magnitudes (non-finite values are skipped);
@@ -661,8 +656,8 @@ otf_tlayout_kernel(LevelSrc src, OtfGeom g, float s, __bf16* __restrict__ dst, u
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float v = cin ? xv[e] * s : 0.f;
-        hi[e] = (__bf16)v;
-        lo[e] = (__bf16)(v - (float)hi[e]);
+        hi[e] = bf16_hi(v);
+        lo[e] = bf16_lo(v, hi[e]);
         m = __builtin_isfinite(v) ? fmaxf(m, fabsf(v)) : m;
     }
     if (in) {
@@ -671,24 +666,6 @@ otf_tlayout_kernel(LevelSrc src, OtfGeom g, float s, __bf16* __restrict__ dst, u
         if constexpr (X3) *reinterpret_cast<bf16x8*>(o + 64 * 8) = lo;
     }
     if (vmax) max_abs_finite(vmax, m);
-}
-
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        hi[e] = (__bf16)v[e];
-        lo[e] = (__bf16)(v[e] - (float)hi[e]);
-    }
-}
-
-template <bool X3>
-__device__ __forceinline__ void mma3(f32x16& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh,
-                                     const bf16x8& bl) {
-    if constexpr (X3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
 struct BwdArgs {
@@ -936,11 +913,11 @@ otf_backward_kernel(BwdArgs a) {
                     *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(gr);
                     *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(gr + 4);
                     bf16x8 ah, al;
-                    split8(v, ah, al);
+                    split<3>(v, ah, al);                     // bf16 mode: al goes unused (split<1> reschedules)
                     const __bf16* pn = seg_ptr(min(s + 1, nseg - 1));
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        if (t < ntn) mma3<X3>(accq[t], ah, al, bh[t], bl[t]);
+                        if (t < ntn) mma<X3 ? 3 : 1>(accq[t], ah, al, bh[t], bl[t]);
                         const __bf16* pp = pn + (size_t)(nt0 + min(t, ntn - 1)) * unit;
                         bh[t] = *reinterpret_cast<const bf16x8*>(pp);
                         bl[t] = X3 ? *reinterpret_cast<const bf16x8*>(pp + 64 * 8) : bh[t];
@@ -977,21 +954,21 @@ otf_backward_kernel(BwdArgs a) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] = G[(ks * 16 + 8 * h + e) * kBwdLd + mt * 32 + j32];
                         bf16x8 ah, al;
-                        split8(v, ah, al);
+                        split<3>(v, ah, al);
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
-                            if (t0 + t < ntn) mma3<X3>(accp[t], ah, al, qh[t], ql[t]);
+                            if (t0 + t < ntn) mma<X3 ? 3 : 1>(accp[t], ah, al, qh[t], ql[t]);
                             load_q(min(ks + 1, kBwdQ / 16 - 1), t);
                         }
                     }
-                    // lane (channel j32, half h): register 4i + k is band target mt*32 + 8i + 4h + k
+                    // lane (channel j32, half h): register v is band target mt*32 + acc_row(v, h)
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
                         const int ch = (nt0 + t0 + t) * 32 + j32;
                         if (t0 + t >= ntn || ch >= g.C) continue;
 #pragma unroll
                         for (int v = 0; v < 16; ++v) {
-                            const int jt = mt * 32 + 8 * (v >> 2) + 4 * h + (v & 3);
+                            const int jt = mt * 32 + acc_row(v, h);
                             const int s = jt >> 4;
                             if (s >= nseg) continue;
                             const int tx = bseg_x[s] * 16 + (jt & 15);
@@ -1011,7 +988,7 @@ otf_backward_kernel(BwdArgs a) {
             }
         }
     }
-    // ---- d fmap1 (planar) += scale * d q~: lane (channel j32, half h), register 4i + k = query x 8i+4h+k ----
+    // ---- d fmap1 (planar) += scale * d q~: lane (channel j32, half h), register v = query x acc_row(v, h) ----
     const int y = qy0 + mt;
     if (y < g.H) {
 #pragma unroll
@@ -1022,7 +999,7 @@ otf_backward_kernel(BwdArgs a) {
             float* o = a.gq + ((size_t)b * g.C + ch) * N + (size_t)y * g.W + qx0;
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int x = 8 * (v >> 2) + 4 * h + (v & 3);
+                const int x = acc_row(v, h);
                 if (qx0 + x < g.W) o[x] += a.scale * accq[t][v];
             }
         }
@@ -1260,12 +1237,11 @@ BwdLayout bwd_layout(int B, int C, int H, int W, int L, int compute) {
         p += (long long)y.g.lh[l] * y.g.lw[l];
     }
     y.pT = p;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     y.pt_off = 0;
-    y.qt_off = up(tbytes);
-    y.dp_off = y.qt_off + up(qbytes);
-    y.nf_off = y.dp_off + up((size_t)B * p * C * sizeof(long long));
-    y.sc_off = y.nf_off + up((size_t)B * p * C * sizeof(float));
+    y.qt_off = align256(tbytes);
+    y.dp_off = y.qt_off + align256(qbytes);
+    y.nf_off = y.dp_off + align256((size_t)B * p * C * sizeof(long long));
+    y.sc_off = y.nf_off + align256((size_t)B * p * C * sizeof(float));
     y.total = y.sc_off + 512;
     return y;
 }

@@ -20,7 +20,7 @@
 //    64 queries x 256 targets per workgroup, K staged through LDS in 64-deep chunks.
 // Operands are first transposed to pixel-major, channel-contiguous (B, N, Cp) by prep_operand.
 
-#include "rmd_common.h"
+#include "mfma_bf16.h"
 #include "corr_x3.h"
 
 #include <cstdlib>
@@ -33,10 +33,6 @@ constexpr int kThreads = 256;
 constexpr int kBQ = 64;      // queries per workgroup (tiled kernel)
 constexpr int kNT = 256;     // targets per workgroup (16 x 16 block)
 constexpr int kKC = 64;      // K chunk staged in LDS (tiled kernel)
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 template <bool F32> struct Operand { using T = __bf16; static constexpr int S = 2; };
 template <> struct Operand<true> { using T = float; static constexpr int S = 4; };
@@ -684,9 +680,6 @@ __device__ __forceinline__ void swp(unsigned& x, unsigned& y) {
     x = r[0];
     y = r[1];
 }
-
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
 
 // lane-dependent parts of the store offsets of query slot q (bytes)
 struct LaneOff {

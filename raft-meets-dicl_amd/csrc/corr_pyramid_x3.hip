@@ -18,22 +18,15 @@
 // blocks' query tiles (X3Sched).  The 32x32x16 form of rounds 2-4 is in git history (commit db30b41 and before;
 // profiles/x3_ab_r05.json compares them).
 
-#include "rmd_common.h"
+#include "mfma_bf16.h"
 #include "corr_x3.h"
 
 namespace rmd {
 namespace x3 {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
 constexpr int kBlockRows = 8, kBlockCols = 16;
 constexpr unsigned kBig = 0x40000000u;      // offset bias beyond every level's range
-
-__device__ __forceinline__ __bf16 hi_part(float v) { return (__bf16)v; }
-__device__ __forceinline__ __bf16 lo_part(float v) { return (__bf16)(v - (float)(__bf16)v); }
 
 // ---- operand prep: both feature maps, split, in one launch ------------------------------------
 // grid (128-pixel tiles, B, 2).  z = 0: fmap2 * scale -> A hi / lo, pixel-major (B, N, 256);
@@ -86,8 +79,8 @@ prep_split(const float* __restrict__ f1, const float* __restrict__ f2, __bf16* _
             bf16x8 hi, lo;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                hi[e] = hi_part(v[e][i]);
-                lo[e] = lo_part(v[e][i]);
+                hi[e] = bf16_hi(v[e][i]);
+                lo[e] = bf16_lo(v[e][i], hi[e]);
             }
             *reinterpret_cast<bf16x8*>(tHi + (size_t)(4 * q + i) * kStride + cg * 16) = hi;
             *reinterpret_cast<bf16x8*>(tLo + (size_t)(4 * q + i) * kStride + cg * 16) = lo;
@@ -206,7 +199,6 @@ __device__ __forceinline__ void swap16(unsigned& x, unsigned& y) {
 // ((p * 32 + cc) * 128 + r) * 16, row r = 16 mt + 8 (row in pair) + col in half.  A fragment read
 // (lane n + 16 g: row 16 mt + n, chunk 4 s + g) gives every 16-lane ds_read_b128 group 16 distinct rows
 // = 16 distinct 16-B bank slots (no padding, 128 KiB).
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 constexpr int kLds16 = 2 * 32 * 128 * 16;
 constexpr int kDR16 = 4;                     // B ring depth (k-steps of 32 channels; divides 8)
 constexpr int kEpiStores16 = 30;             // buffer stores of one epilogue16 (16 + 8 + 4 + 2)

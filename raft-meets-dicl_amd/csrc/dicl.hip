@@ -14,7 +14,7 @@
 // displacement plane, so every store is a 16-byte-per-lane, fully coalesced row of the contiguous
 // (B, du, dv, 2C(+2), h, w) MatchingNet input; the f1 half is re-read from L2 per displacement.
 
-#include "rmd_common.h"
+#include "mfma_bf16.h"
 #include "dicl_taps.h"
 
 #include <algorithm>
@@ -1198,16 +1198,10 @@ dap_kernel(const float* __restrict__ x, const float* __restrict__ wgt, int D, in
     }
 }
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 dbf16x8_t;
-typedef __attribute__((ext_vector_type(4))) __bf16 dbf16x4_t;
-
 // ---- DAP as a split-bf16 (x3) MFMA GEMM (product form) -----------------------------------------
-// out_b (D x n) = W (D x D) . x_b (D x n), fp32 accuracy from three bf16 products per k-step,
-// v = hi + lo, hi = bf16(v), lo = bf16(v - hi):  acc += W_lo.x_hi + W_hi.x_lo + W_hi.x_hi  (the
-// dropped lo.lo term is ~2^-16 relative; same split as the fp32-mode correlation GEMM).  The exact
-// f32 MFMA (v_mfma_f32_32x32x2_f32) runs at 1/16 of the bf16 rate and held the round-1 kernel at
-// ~25 % of even that peak (0.27 ms at D = 324); here the 3 bf16 products cost 3/16.
+// out_b (D x n) = W (D x D) . x_b (D x n), fp32 accuracy from the three bf16 products per k-step of
+// mfma_bf16.h.  The exact f32 MFMA (v_mfma_f32_32x32x2_f32) held the round-1 kernel at ~25 % of even
+// its own peak, 1/16 of the bf16 rate (0.27 ms at D = 324); here the 3 bf16 products cost 3/16.
 // Geometry: a workgroup owns an M-block of MT x 32 output displacements (all of them when D <= 128)
 // and one chunk of the batch image's 32-pixel tiles.  The block's W rows (or W^T rows, transpose)
 // are split once into hi / lo bf16 in LDS — rows of 2 Kp + 16 bytes, an odd number of 16-B slots,
@@ -1225,14 +1219,6 @@ typedef __attribute__((ext_vector_type(4))) __bf16 dbf16x4_t;
 constexpr int kDapSG = 4;     // W staging: 4-element groups per thread in flight
 constexpr int kDapStoreAux = 2;   // output store cache policy (gfx950 cpol: 2 = nt): 10-15 % at D <= 81
 constexpr int kDapKC = 8, kDapNB = 2;   // x ring: NB buffers of KC k-steps
-
-__device__ __forceinline__ void dap_split8(const float* v, dbf16x8_t& hi, dbf16x8_t& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (__bf16)v[j];
-        lo[j] = (__bf16)(v[j] - (float)hi[j]);
-    }
-}
 
 template <int MT, int NW, int AUX, int KC, int NB>
 __global__ void __launch_bounds__(NW * 64, 2)
@@ -1314,20 +1300,16 @@ dap_x3_kernel(const float* __restrict__ x, const float* __restrict__ wgt, int D,
 #pragma unroll
             for (int g = 0; g < kDapSG; ++g) {
                 if (ro[g] < 0) continue;
-                dbf16x4_t hi, lo;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    hi[q] = (__bf16)v[g][q];
-                    lo[q] = (__bf16)(v[g][q] - (float)hi[q]);
-                }
-                *reinterpret_cast<dbf16x4_t*>(sh + ro[g]) = hi;
-                *reinterpret_cast<dbf16x4_t*>(sl + ro[g]) = lo;
+                bf16x4 hi, lo;
+                split<3>(v[g], hi, lo);
+                *reinterpret_cast<bf16x4*>(sh + ro[g]) = hi;
+                *reinterpret_cast<bf16x4*>(sl + ro[g]) = lo;
             }
         }
     }
     __syncthreads();
 
-    f32x16_t acc[MT];
+    f32x16 acc[MT];
     for (int i0 = 0; i0 < nsteps; i0 += NB) {
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
@@ -1338,35 +1320,32 @@ dap_x3_kernel(const float* __restrict__ x, const float* __restrict__ wgt, int D,
             const int c = i % nch;
             if (c == 0) {
 #pragma unroll
-                for (int m = 0; m < MT; ++m) acc[m] = f32x16_t{};
+                for (int m = 0; m < MT; ++m) acc[m] = f32x16{};
             }
 #pragma unroll
             for (int uu = 0; uu < KC; ++uu) {
                 const int s = c * KC + uu;
                 if (s < nks) {
-                    dbf16x8_t bh, bl;
-                    dap_split8(xb[u] + uu * 8, bh, bl);
+                    bf16x8 bh, bl;
+                    split<3>(xb[u] + uu * 8, bh, bl);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         const unsigned a = aoff + (unsigned)(m * 32 * RB + 32 * s);
-                        const dbf16x8_t ah = *reinterpret_cast<const dbf16x8_t*>(sh + a);
-                        const dbf16x8_t al = *reinterpret_cast<const dbf16x8_t*>(sl + a);
-                        f32x16_t cacc = acc[m];
-                        cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, cacc, 0, 0, 0);
-                        cacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, cacc, 0, 0, 0);
-                        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, cacc, 0, 0, 0);
+                        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(sh + a);
+                        const bf16x8 al = *reinterpret_cast<const bf16x8*>(sl + a);
+                        mma<3>(acc[m], ah, al, bh, bl);
                     }
                 }
             }
             if (c == nch - 1) {
-                // C tile: lane (r, h) holds rows 8 (e >> 2) + 4 h + (e & 3) of pixel column r
+                // C tile: lane (r, h) holds rows acc_row(e, h) of pixel column r; 4 h is in the lane offset
                 const int p = (t0 + (i / nch) * tstride) * 32 + r;
                 const unsigned so = p < n ? (unsigned)(4 * h) * rowb + (unsigned)p * 4u : 0x80000000u;
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const unsigned row = (unsigned)(o0 + m * 32 + 8 * (e >> 2) + (e & 3));
+                        const unsigned row = (unsigned)(o0 + m * 32 + acc_row(e, 0));
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(acc[m][e]), orr, (int)(so + row * rowb),
                                                               0, AUX);
                     }
@@ -1782,7 +1761,7 @@ namespace {
 // are 8 consecutive pixels of one row (two float4 loads) split in registers.
 constexpr int kWgPx = 16;                        // pixels per MFMA k-step
 
-__device__ __forceinline__ void wg_frag(const float* __restrict__ row, bool rok, int p, int n, dbf16x8_t& hi, dbf16x8_t& lo) {
+__device__ __forceinline__ void wg_frag(const float* __restrict__ row, bool rok, int p, int n, bf16x8& hi, bf16x8& lo) {
     float v[8];
     if (rok && p + 7 < n && ((reinterpret_cast<uintptr_t>(row + p) & 15) == 0)) {
         *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(row + p);
@@ -1791,11 +1770,7 @@ __device__ __forceinline__ void wg_frag(const float* __restrict__ row, bool rok,
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (rok && p + e < n) ? row[p + e] : 0.f;
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        hi[e] = (__bf16)v[e];
-        lo[e] = (__bf16)(v[e] - (float)hi[e]);
-    }
+    split<3>(v, hi, lo);
 }
 
 // grid (B * nchunk, tile groups); 256 threads; part (splits, Dp, Dp)
@@ -1812,14 +1787,14 @@ dap_wgrad_kernel(const float* __restrict__ g, const float* __restrict__ x, int D
     const int p0 = c * pchunk, p1 = min(n, p0 + pchunk);
     const float* gb = g + (size_t)b * D * n;
     const float* xb = x + (size_t)b * D * n;
-    f32x16_t acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int v = 0; v < 2; ++v) acc[u][v] = f32x16_t{};
+        for (int v = 0; v < 2; ++v) acc[u][v] = f32x16{};
     const int o[2] = {32 * ot0 + j, 32 * (ot0 + 1) + j}, i[2] = {32 * it0 + j, 32 * (it0 + 1) + j};
     for (int p = p0; p < p1; p += kWgPx) {
-        dbf16x8_t ah[2], al[2], bh[2], bl[2];
+        bf16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             wg_frag(gb + (size_t)min(o[u], D - 1) * n, o[u] < D, p + 8 * h, p1, ah[u], al[u]);
@@ -1828,13 +1803,10 @@ dap_wgrad_kernel(const float* __restrict__ g, const float* __restrict__ x, int D
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[u], bh[v], acc[u][v], 0, 0, 0);
-                acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[u], bl[v], acc[u][v], 0, 0, 0);
-                acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[u], bh[v], acc[u][v], 0, 0, 0);
-            }
+            for (int v = 0; v < 2; ++v) mma<3>(acc[u][v], ah[u], al[u], bh[v], bl[v]);
     }
-    // lane (column j, half h): register 4r + k is row 8r + 4h + k of the tile
+    // lane (column j, half h): register r is row acc_row(r, h) of the tile (spelled out: through acc_row the
+    // compiler swaps the operands of one v_or_b32)
     float* ps = part + (size_t)s * Dp * Dp;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -2014,7 +1986,7 @@ extern "C" int rmd_warp_backwards_backward(const float* grad_out, const float* f
 extern "C" size_t rmd_dicl_stack_int_warped_workspace_bytes(int batch, int channels, int height, int width) {
     if (batch < 1 || channels < 1 || height < 1 || width < 1) return 0;
     const size_t n = (size_t)height * width;
-    return ((size_t)batch * channels * n * sizeof(float) + 2 * (size_t)batch * n + 255) & ~(size_t)255;
+    return align256((size_t)batch * channels * n * sizeof(float) + 2 * (size_t)batch * n);
 }
 
 extern "C" int rmd_dicl_stack_int_warped(const float* fmap1, const float* fmap2, const float* flow, int batch,

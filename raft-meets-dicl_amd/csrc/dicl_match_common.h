@@ -3,7 +3,8 @@
 // shapes and their instance classes, the weight pack kernel, and the forward of the MLP up to the layer-2
 // activations.  The backward recomputes the forward with these very templates (NP = 3), so the two kernels
 // cannot disagree on the sample, the products or their order; tests/test_gpu_dicl_match_digest.py pins the
-// outputs of both bit for bit.
+// outputs of both bit for bit.  The split-bf16 arithmetic itself (types, split, mma<NP>, acc_row) is
+// mfma_bf16.h's, shared with every other MFMA kernel.
 //
 // Orientation (one wave, v_mfma_f32_32x32x16_bf16): 32 samples — 32 consecutive pixels at ONE
 // displacement — sit on the MFMA column (lane & 31), channels on the row; weights are the A operand,
@@ -16,12 +17,9 @@
 #pragma once
 
 #include "dicl_taps.h"
-#include "rmd_common.h"
+#include "mfma_bf16.h"
 
 namespace rmd {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 constexpr int kMaxWidth = 128;                 // hidden widths and 2C
 constexpr int kBiasBytes = 4 * kMaxWidth * 4;  // t1, t2, t3, w4 in LDS
@@ -106,9 +104,6 @@ __host__ __device__ __forceinline__ int frag_k(int ks, int hh, int j) { return 1
 // frag_k without the lane-half term: the wave-uniform part of a fragment element's channel
 __device__ __forceinline__ int frag_k_uniform(int ks, int j) { return 16 * ks + 8 * (j >> 2) + (j & 3); }
 
-// accumulator row of register i for lane half hh (32x32 C/D map)
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
-
 // ---- weights -> A fragments ------------------------------------------------------------------------
 
 // the matrices of the pack kernel: A[row][k] = src[row * row_stride + k * k_stride]; matrix m owns the
@@ -165,8 +160,8 @@ dicl_match_pack_kernel(PackDesc D, int nfrag, int lo, bf16x8* __restrict__ frags
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float v = row[(size_t)frag_k(ks, lane >> 5, j) * k_stride];
-        hi[j] = (__bf16)v;
-        lopart[j] = (__bf16)(v - (float)hi[j]);
+        hi[j] = bf16_hi(v);
+        lopart[j] = bf16_lo(v, hi[j]);
     }
     // first[3] == nfrag: plain fragments fill parts 0 / 1, transposed ones parts 2 / 3
     const int orient = fa >= nfrag ? 1 : 0;
@@ -189,27 +184,6 @@ __device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwis
 // a float at a 32-bit byte offset from a wave-uniform base (scalar base + vector offset addressing)
 __device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-// NP: bf16 products per layer (3, or 1 for RMD_BF16, which keeps no lo parts)
-template <int NP>
-__device__ __forceinline__ void split8(const float* v, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (__bf16)v[j];
-        if constexpr (NP == 3) lo[j] = (__bf16)(v[j] - (float)hi[j]);
-    }
-}
-
-// acc += A . B with NP bf16 products: hi.hi, and for NP == 3 also lo.hi and hi.lo (small terms first)
-template <int NP>
-__device__ __forceinline__ void mma(f32x16& acc, const bf16x8& ah, const bf16x8& al, const bf16x8& bh,
-                                    const bf16x8& bl) {
-    if constexpr (NP == 3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
 // t1 | t2 | t3 | w4 into LDS, kMaxWidth floats each, zero past a layer's width (the caller synchronises)
@@ -250,7 +224,7 @@ __device__ __forceinline__ void f1_frags(const float* f1b, int n, unsigned off1,
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = ld_off(f1b + (size_t)frag_k_uniform(ks, j) * n, off1);
-            split8<NP>(v, xh[ks], xl[ks]);
+            split<NP>(v, xh[ks], xl[ks]);
         }
     }
 }
@@ -292,7 +266,7 @@ __device__ __forceinline__ void f2_frags(const float* f2b, int n, unsigned half_
                 v[j] = t.wgt[0] * ld_off(fc, off2[0]) + t.wgt[1] * ld_off(fc, off2[1]) +
                        t.wgt[2] * ld_off(fc, off2[2]) + t.wgt[3] * ld_off(fc, off2[3]);
             }
-            split8<NP>(v, xh[ks], xl[ks]);
+            split<NP>(v, xh[ks], xl[ks]);
         }
     }
 }
@@ -311,7 +285,7 @@ __device__ __forceinline__ unsigned relu_frags(const f32x16& acc, const float* b
             if constexpr (MASK) m |= (z > 0.f ? 1u : 0u) << (8 * s + j);
             v[j] = relu_nan(z);
         }
-        split8<NP>(v, ah[s], al[s]);
+        split<NP>(v, ah[s], al[s]);
     }
     return m;
 }

@@ -228,8 +228,8 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
                         gw4[mo] += tile_rowsum(ag, red, lane);
                         gt3[mo] += tile_rowsum(dz, red, lane);
                     }
-                    split8<3>(dz, d3h[2 * mo], d3l[2 * mo]);
-                    split8<3>(dz + 8, d3h[2 * mo + 1], d3l[2 * mo + 1]);
+                    split<3>(dz, d3h[2 * mo], d3l[2 * mo]);
+                    split<3>(dz + 8, d3h[2 * mo + 1], d3l[2 * mo + 1]);
                 }
             }
 
@@ -258,8 +258,8 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
 #pragma unroll
                     for (int i = 0; i < 16; ++i) dz[i] = ((mask2[mo] >> i) & 1u) ? acc[i] : 0.f;
                     if (params) gt2[mo] += tile_rowsum(dz, red, lane);
-                    split8<3>(dz, d2h[2 * mo], d2l[2 * mo]);
-                    split8<3>(dz + 8, d2h[2 * mo + 1], d2l[2 * mo + 1]);
+                    split<3>(dz, d2h[2 * mo], d2l[2 * mo]);
+                    split<3>(dz + 8, d2h[2 * mo + 1], d2l[2 * mo + 1]);
                 }
             }
 
@@ -288,8 +288,8 @@ dicl_match_grad_kernel(const float* __restrict__ gcost, const float* __restrict_
 #pragma unroll
                     for (int i = 0; i < 16; ++i) dz[i] = ((mask1[mo] >> i) & 1u) ? acc[i] : 0.f;
                     if (params) gt1[mo] += tile_rowsum(dz, red, lane);
-                    split8<3>(dz, d1h[2 * mo], d1l[2 * mo]);
-                    split8<3>(dz + 8, d1h[2 * mo + 1], d1l[2 * mo + 1]);
+                    split<3>(dz, d1h[2 * mo], d1l[2 * mo]);
+                    split<3>(dz + 8, d1h[2 * mo + 1], d1l[2 * mo + 1]);
                 }
             }
 
@@ -420,8 +420,6 @@ dicl_match_grad_reduce_kernel(const float* __restrict__ partw, const float* __re
 }
 
 int grad_grid(int batch, long long n) { return (int)std::min<long long>((long long)batch * ((n + 31) / 32), kCUs); }
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Layout {
     size_t frag_bytes, partw_off, partv_off, total;

@@ -9,8 +9,8 @@
 // (z and r together) and the candidate kernel (q and the gating) only z and r.h pass through the workspace.
 //
 // Each convolution is a GEMM with M = output channels, N = pixels, K = 5 (Hd + Xd); v_mfma_f32_32x32x16_bf16
-// with the weights as the A operand and the pixels on the MFMA column (lane & 31), bf16x8 / f32x16 / mma<NP>
-// as in dicl_match_common.h.  The B operand is an implicit im2col: a workgroup owns a segment of kTile
+// with the weights as the A operand and the pixels on the MFMA column (lane & 31), the split-bf16 arithmetic
+// of mfma_bf16.h.  The B operand is an implicit im2col: a workgroup owns a segment of kTile
 // pixels of one image row and stages, per chunk of KC input channels, the positions its five taps read
 // (kTile + 4 along the row for axis 0, five row segments for axis 1) through LDS as bf16 (hi, and the bf16
 // of the residual in the three-product mode), position-major with the channels of a position contiguous:
@@ -24,7 +24,7 @@
 // The summation order of an output is fixed (channel chunk, tap, k-step; small products first) and does not
 // depend on the batch or on the other tiles: results are bitwise repeatable and per-sample independent.
 
-#include "dicl_match_common.h"
+#include "mfma_bf16.h"
 
 namespace rmd {
 namespace {
@@ -45,8 +45,6 @@ struct GruGeom {
 inline bool gru_supported(int hd, int xd) {
     return hd >= 32 && hd <= 32 * kWaves && hd % 32 == 0 && xd >= 16 && xd % 16 == 0 && hd + xd <= 512;
 }
-
-inline size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 // ---- weights -> A fragments --------------------------------------------------------------------------
 
@@ -72,8 +70,8 @@ gru_pack_kernel(GruWeights Wt, int ngates, int mo, int ks, int C, int nfrag, int
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float v = row[j * kTaps];
-        hi[j] = (__bf16)v;
-        lopart[j] = (__bf16)(v - (float)hi[j]);
+        hi[j] = bf16_hi(v);
+        lopart[j] = bf16_lo(v, hi[j]);
     }
     frags[id] = hi;
     if (lo) frags[id + (size_t)nfrag * 64] = lopart;
@@ -139,7 +137,7 @@ gru_kernel(const float* __restrict__ hsrc, const float* __restrict__ x, const bf
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = inside ? src[j * HW] : 0.f;
             bf16x8 hi, lo;
-            split8<NP>(v, hi, lo);
+            split<NP>(v, hi, lo);
             *reinterpret_cast<bf16x8*>(&sm[s * S::STRIDE + 8 * grp]) = hi;
             if constexpr (NP == 3) *reinterpret_cast<bf16x8*>(&sm[(S::SLOTS + s) * S::STRIDE + 8 * grp]) = lo;
         }
@@ -218,12 +216,6 @@ void run_half(int np, int axis, const float* h, const float* x, const bf16x8* fr
     }
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const char* pa = static_cast<const char*>(a);
-    const char* pb = static_cast<const char*>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
 size_t gru_workspace_bytes(int batch, int hd, int xd, int height, int width) {
     const size_t packed = (size_t)6 * hd * kTaps * (hd + xd) * 2 * sizeof(__bf16);
     const size_t map = (size_t)batch * hd * height * width * sizeof(float);
@@ -276,9 +268,9 @@ struct GruWork {
 
 GruWork gru_prepare(const float* const* weights, int ngates, void* workspace, const GruGeom& P, bool lo,
                     hipStream_t st) {
-    char* base = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(workspace)));
+    char* base = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(workspace)));
     const size_t packed = (size_t)6 * P.Hd * kTaps * P.C * 2 * sizeof(__bf16);       // a multiple of kAlign
-    const size_t map = align_up((size_t)P.B * P.Hd * P.H * P.W * sizeof(float));
+    const size_t map = align256((size_t)P.B * P.Hd * P.H * P.W * sizeof(float));
     GruWork Wk;
     Wk.frags = reinterpret_cast<bf16x8*>(base);
     Wk.zbuf = reinterpret_cast<float*>(base + packed);

@@ -369,8 +369,6 @@ loss_backward_up_kernel(LossTable t, const float* __restrict__ target, const uns
     }
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 inline int forward_blocks(int batch, int height, int width) {
     const long long items = (long long)batch * height * width;       // the scalar path's item count (the larger)
     const long long blocks = (items + kThreads - 1) / kThreads;

@@ -266,8 +266,6 @@ metrics_final_kernel(const long long* __restrict__ part, int nblocks, int n, int
     stats[idx] = r;                                // (N, B, kSlots)
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
 // blocks per sample the workspace is sized for: the scalar path's tile count, bounded

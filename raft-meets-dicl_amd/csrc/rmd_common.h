@@ -94,6 +94,20 @@ __host__ __device__ constexpr int level_chunk(int l) { return l <= 1 ? 8 : (l ==
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// ---- buffers (host) ----------------------------------------------------------------------------
+// v rounded up to the 256-byte granule of every workspace carve-up
+inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// p on an a-byte boundary (a a power of two)
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// do the byte ranges [a, a + na) and [b, b + nb) meet
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char* pa = static_cast<const char*>(a);
+    const char* pb = static_cast<const char*>(b);
+    return pa < pb + nb && pb < pa + na;
+}
+
 // XCD-aware block order: the dispatcher deals workgroups of a 1-D grid round-robin over the 8 XCDs
 // (block i -> XCD i mod 8); remap so that XCD k runs the k-th contiguous eighth of the logical
 // block range, keeping what consecutive logical blocks share (one batch image's feature maps) in
