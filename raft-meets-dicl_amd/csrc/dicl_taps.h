@@ -1,6 +1,6 @@
-// dicl_taps.h — the bilinear taps of one DICL sample position, shared by the stack kernels (dicl.hip) and the
-// fused dicl-1x1 cost (dicl_match.hip, dicl_match_grad.hip): every kernel that gathers from fmap2 or scatters
-// into its gradient means the same sample by it.
+// dicl_taps.h — the bilinear taps of one DICL sample position, shared by the stack kernels (dicl_stack.hip,
+// dicl_stack_backward.hip) and the fused dicl-1x1 cost (dicl_match.hip, dicl_match_grad.hip): every kernel
+// that gathers from fmap2 or scatters into its gradient means the same sample by it.
 #pragma once
 
 #include "rmd_common.h"

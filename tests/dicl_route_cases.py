@@ -2,7 +2,7 @@
 rmd_dicl_stack / rmd_dicl_stack_backward, with the route each shape must take, and the inputs the
 GPU parity tests feed them (built once per process and never modified).
 
-The expected routes restate the dispatch rule of csrc/dicl.hip by hand (radius, grid scale
+The expected routes restate the dispatch rule of csrc/dicl_stack.h by hand (radius, grid scale
 sx = (wl-1)/(nw-1), sy = (hl-1)/(nh-1), LDS window estimate against 4096 / 12288 floats, stack size);
 they were not read back from the library.  A row whose route moves (a retuned window threshold, a
 new kernel) fails test_dicl_routes.py: move the shape so the route stays covered.

@@ -67,3 +67,8 @@ def test_workspace_sizes_are_those_of_the_build_before_the_shared_helpers():
     assert L.rmd_corr_otf_backward_workspace_bytes(1, 48, 21, 35, 3, bf16) == 854272
     # the warped DICL volume at warp_dicl_cost_b2_c16_10x12
     assert L.rmd_dicl_stack_int_warped_workspace_bytes(2, 16, 10, 12) == 15872
+    # the host code that moved out of dicl.hip with its operators (dicl_int.hip, dap.hip): the unwarped volume
+    # at the same shape, the DAP weight gradient at D = 81 on a few pixels and at the 'full' D = 324 of cfg4
+    assert L.rmd_dicl_stack_int_workspace_bytes(2, 10, 12) == 240
+    assert L.rmd_dap_weight_grad_workspace_bytes(2, 81, 120) == 147456
+    assert L.rmd_dap_weight_grad_workspace_bytes(8, 324, 7680) == 11894784
