@@ -18,8 +18,7 @@
 // blocks' query tiles (X3Sched).  The 32x32x16 form of rounds 2-4 is in git history (commit db30b41 and before;
 // profiles/x3_ab_r05.json compares them).
 
-#include "mfma_bf16.h"
-#include "corr_x3.h"
+#include "corr_pyramid.h"
 
 namespace rmd {
 namespace x3 {
@@ -144,12 +143,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rebase(const Lvl& L, unsigned 
 
 __device__ __forceinline__ unsigned soff(const Lvl& L, int row, int chunk) {
     return (row < L.rows && chunk < L.chunks) ? (unsigned)row * L.rs + (unsigned)chunk * L.cs : kBig;
-}
-
-__device__ __forceinline__ void swap32(unsigned& x, unsigned& y) {
-    auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
 }
 
 __device__ __forceinline__ void swapf(float& x, float& y) {

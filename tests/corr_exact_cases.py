@@ -297,7 +297,10 @@ PYRAMID_CASES = [
     # w8 (bf16 operands, fp16 tiles layout, channels padding to 256)
     _pc("b2c256-16x24", "bf16", "base", 2, 256, 16, 24, 1 / 16, "w8", "f16"),
     _pc("b1c193-17x33", "bf16", "base", 1, 193, 17, 33, 1 / 16, "w8", "f16"),          # zero-padded channels, ragged
-    _pc("b2c256-40x64", "bf16", "base", 2, 256, 40, 64, 1 / 16, "w8", "f16"),          # paired last block row
+    _pc("b2c256-40x64", "bf16", "base", 2, 256, 40, 64, 1 / 16, "w8", "f16"),          # last block row of 8, query tiles split 4 ways: not paired
+    # paired last block row (w8_balance: fewer than 32 query tiles, so no query split; W % 32 == 0; last row <= 8)
+    _pc("b1c256-24x32", "bf16", "base", 1, 256, 24, 32, 1 / 16, "w8", "f16"),          # second half stores rows on every level
+    _pc("b1c256-18x32", "bf16", "base", 1, 256, 18, 32, 1 / 16, "w8", "f16"),          # second half mostly past the map
     _pc("b1c256-23x96", "bf16", "base", 1, 256, 23, 96, 1 / 16, "w8", "f16"),          # odd column blocks
     _pc("b2c16p256-16x24", "bf16", "digest", 2, 16, 16, 24, 1 / 4, "w8", "f16", 256),  # digest kind bf16-tiles
     _pc("b2c16p256-15x20", "bf16", "digest", 2, 16, 15, 20, 1 / 4, "w8", "f16", 256),  # 1-pixel level 3

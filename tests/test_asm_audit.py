@@ -4,7 +4,7 @@ corr_pyramid_w8 (the default bf16 path): no scratch, accumulators in VGPRs (no v
 round trips), exactly 128 MFMAs and 23 buffer stores per 32-query tile, every store range-checked
 (buffer_store ... offen), the B-fragment loads coalesced global_load_dwordx4.
 
-corr_pyramid_stationary<2, 0> (the product path for maps whose 32-bit store offsets would overflow,
+corr_pyramid_stationary (the product path for maps whose 32-bit store offsets would overflow,
 e.g. 4K frames; GPU test: test_gpu_corr.py::test_stationary_path_4k_sampled_vs_oracle):
 
 The kernel issues its B-fragment loads in inline asm and retires them with ONE hand-placed
@@ -25,8 +25,9 @@ from conftest import ROOT
 
 HIPCC = "/opt/rocm/bin/hipcc"
 HIPFLAGS = ["-fno-slp-vectorize"]      # as raft-meets-dicl_amd/csrc/Makefile
-SRC = os.path.join(ROOT, "raft-meets-dicl_amd", "csrc", "corr_pyramid.hip")
-STORES_PER_TILE = {1: 12, 2: 23}      # STraits<TH>::kStores
+CSRC = os.path.join(ROOT, "raft-meets-dicl_amd", "csrc")
+SRC = [os.path.join(CSRC, "corr_pyramid_stationary.hip"), os.path.join(CSRC, "corr_pyramid_w8.hip")]
+STORES_PER_TILE = {2: 23}      # corr_pyramid_stationary.hip kStores
 
 
 def _regs(line):
@@ -42,24 +43,26 @@ def _regs(line):
 def module_asm():
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    tmp = tempfile.mkdtemp()
-    try:
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include",
-                        f"-I{os.path.dirname(SRC)}", "-save-temps", *HIPFLAGS, "-c", SRC, "-o", os.path.join(tmp, "x.o")],
-                       cwd=tmp, check=True, capture_output=True, timeout=600)
-        s = [f for f in os.listdir(tmp) if f.endswith(".s") and "gfx950" in f][0]
-        txt = open(os.path.join(tmp, s)).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+    txt = ""
+    for src in SRC:
+        tmp = tempfile.mkdtemp()
+        try:
+            subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include",
+                            f"-I{CSRC}", "-save-temps", *HIPFLAGS, "-c", src, "-o", os.path.join(tmp, "x.o")],
+                           cwd=tmp, check=True, capture_output=True, timeout=600)
+            s = [f for f in os.listdir(tmp) if f.endswith(".s") and "gfx950" in f][0]
+            txt += open(os.path.join(tmp, s)).read()
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
     return txt
 
 
 @pytest.fixture(params=[2], ids=["4waves"])
 def kernel_asm(request, module_asm):
     th = request.param
-    m = re.search(rf"^(_ZN3rmd\w*corr_pyramid_stationaryILi{th}ELi0E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+    m = re.search(r"^(_ZN3rmd\w*23corr_pyramid_stationaryE\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                   module_asm, re.S | re.M)
-    assert m, f"stationary<{th}, 0> kernel not found"
+    assert m, "corr_pyramid_stationary kernel not found"
     return th, m.group(2).split("\n")
 
 
@@ -114,8 +117,8 @@ def test_every_asm_load_window_is_exact(kernel_asm):
 
 @pytest.fixture
 def w8_asm(module_asm):
-    m = re.search(r"^(_ZN3rmd\w*corr_pyramid_w8ILi2E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel", module_asm, re.S | re.M)
-    assert m, "corr_pyramid_w8<2> not found"
+    m = re.search(r"^(_ZN3rmd\w*15corr_pyramid_w8E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel", module_asm, re.S | re.M)
+    assert m, "corr_pyramid_w8 not found"
     return m.group(2).split("\n")
 
 

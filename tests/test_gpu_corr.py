@@ -381,11 +381,14 @@ def test_corr_grad_gemm_misaligned_base_pointers(layout):
 
 @pytest.mark.parametrize("b,h,w", [(1, 55, 128), (2, 40, 64), (1, 23, 96), (3, 55, 128), (1, 46, 62)])
 def test_w8_balanced_schedule_levels_vs_oracle(b, h, w):
-    """The bf16 GEMM's balanced schedule (corr_pyramid.hip w8_balance): a last block row of <= 8 target
-    rows is paired two blocks per workgroup (55 = 3*16 + 7; 40 = 2*16 + 8 also stores a level-3 row
-    from the pair's second half), and helper workgroups run the query tiles past qfull.  Every level
-    of sampled queries (including the last query tiles, which the helpers write) against the oracle;
-    (1, 23, 96) has an odd number of column blocks, (1, 46, 62) neither pairs nor splits."""
+    """The bf16 GEMM's schedule (corr_pyramid_w8.hip: w8::pyramid's query split, w8_balance) at shapes with
+    a short last block row (55 = 3*16 + 7, 40 = 2*16 + 8, 23 = 16 + 7).  What they reach is the query split:
+    the blocks alone do not fill the chip, so the query tiles are split 8 ways at (1, 55, 128) and 4 ways at
+    every other shape (no part falls below 16 query tiles); w8_balance pairs the last block row only
+    without a split, so none of these is paired and no helper workgroup exists (the paired prologue is pinned
+    bit for bit by test_gpu_corr_exact.py's 24x32 and 18x32 cases and reached by the full-size b8 runs).
+    (1, 23, 96) has an odd number of column blocks, (1, 46, 62) a last block row of 14 and ragged columns.
+    Every level of sampled queries (the last query tiles included) against the oracle."""
     import rmd
     rng = np.random.default_rng(h * w + b)
     c = 256

@@ -32,7 +32,8 @@ def test_lo_part_expression_is_in_the_header_only():
 
 
 def test_32x32x16_bf16_mfma_is_issued_from_the_header_or_the_single_product_gemm():
-    assert _files_matching(r"__builtin_amdgcn_mfma_f32_32x32x16_bf16") == ["corr_pyramid.hip", HEADER]
+    assert _files_matching(r"__builtin_amdgcn_mfma_f32_32x32x16_bf16") == [
+        "corr_pyramid_stationary.hip", "corr_pyramid_tiled.hip", "corr_pyramid_w8.hip", HEADER]
 
 
 def test_bf16_and_f32x16_vector_types_are_declared_in_the_header_only():

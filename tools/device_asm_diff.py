@@ -2,7 +2,7 @@
 """Prove that a refactor leaves the compiled kernels unchanged: device assembly of REV against this tree,
 kernel by kernel, so a kernel may move to another source.
 
-    python tools/device_asm_diff.py REV
+    python tools/device_asm_diff.py REV [--rename OLD=NEW ...]
 
 Extracts REV's raft-meets-dicl_amd/csrc and include into a temporary directory and builds the device assembly
 of every .hip source there and here (csrc/Makefile's build/asm/%.s rule, this tree's Makefile for both).  Every
@@ -18,6 +18,9 @@ same name, and fall into one class each:
     different   anything else
     missing     in REV only
     new         in this tree only
+
+--rename OLD=NEW (repeatable) replaces the mangled name OLD by NEW throughout REV's assembly before the functions
+are matched, so a kernel whose symbol changed (it lost a template parameter, say) is still compared body for body.
 
 Prints the counts per source of this tree (REV's source for a missing one) and names every function that is not
 identical.  Exit status 1 unless all are identical or reordered.  Needs hipcc, no GPU.
@@ -67,6 +70,10 @@ def functions(source, lines):
             while not re.match(end, lines[j]):
                 j += 1
             (bodies if m else blocks)[(m or k).group(1)] = lines[i:j + 1]
+            # where the assembler's output has the kernel's descriptor before .Lfunc_end, it lies in the body
+            inner = [n for n in range(i, j) if m and re.match(r"\s*\.(end_)?amdhsa_kernel", lines[n])]
+            if inner:
+                blocks[m.group(1)] = lines[inner[0]:inner[-1] + 1]
             i = j
         i += 1
     assert set(blocks) <= set(bodies), f"{source}: .amdhsa_kernel block without a body"
@@ -101,14 +108,22 @@ def classify(a, b):
 
 
 def main():
-    if len(sys.argv) != 2:
+    args, renames = sys.argv[1:], []
+    while "--rename" in args[:-1]:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
+    if len(args) != 1 or args[0].startswith("-") or any(len(r) != 2 for r in renames):
         sys.exit(__doc__)
-    rev = sys.argv[1]
+    rev = args[0]
     with tempfile.TemporaryDirectory() as tmp:
         archive = subprocess.run(["git", "-C", str(ROOT), "archive", rev, CSRC, "include"], check=True,
                                  stdout=subprocess.PIPE).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=archive, check=True)
-        old = collect(build_asm(pathlib.Path(tmp) / CSRC))
+        asm = build_asm(pathlib.Path(tmp) / CSRC)
+    for was, now in renames:
+        asm = {n: [l.replace(was, now) for l in lines] for n, lines in asm.items()}
+    old = collect(asm)
     new = collect(build_asm(ROOT / CSRC))
     # a name keyed with its source on one side only (it was unique there) is keyed alike on both
     for side, other in ((old, new), (new, old)):
