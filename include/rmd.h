@@ -724,6 +724,47 @@ int rmd_sepconv_gru_half(const float* h, const float* x, const float* const* wei
                          float* out, void* workspace, int batch, int hidden, int input, int height, int width,
                          int axis, int compute, void* stream);
 
+/*
+ * Fused k x k convolution, inference only: the convolutions next to the recurrent unit in RAFT's update block
+ * (BasicMotionEncoder raft.py:193-225, FlowHead raft.py:262-273, Up8Network's mask head raft.py:299-331).
+ * A stride-1, "same"-padded dense convolution with bias and activation over the channel concatenation of up to
+ * two float32 NCHW maps, written into a channel slice of a float32 NCHW destination:
+ *   out[b, off + o, y, x] = act(bias[o] + sum_{c,i,j} W[o, c, i, j] in[b, c, y + i - kh/2, x + j - kw/2])
+ *   in = cat(in0 (B, C0, H, W), in1 (B, C1, H, W); NULL exactly when C1 = 0), zero outside the map
+ * weight (Cout, C0 + C1, kh, kw), bias Cout floats, out (B, out_channels_total, H, W) of which only channels
+ * out_offset .. out_offset + Cout - 1 are written (the others are not touched), act 0 = none, 1 = ReLU
+ * (v < 0 ? 0 : v: NaN stays NaN, as torch.relu).  An MFMA implicit GEMM whose operands pass through bfloat16:
+ * compute = RMD_BF16X3 (three split-bf16 products, the parity mode) or RMD_BF16 (one), bias and activation
+ * fp32, as rmd_sepconv_gru.  A NaN input gives NaN in exactly the outputs whose receptive field holds it; a
+ * +-inf input gives NaN there in the parity mode (inf - inf in the residual), the one deviation from the
+ * reference.  Supported (rmd_conv2d_supported, host only; RMD_ERR_SHAPE otherwise): kh, kw odd in 1..7
+ * independently, C0 >= 1, C1 >= 0, C0 + C1 <= 512, Cout in 1..1024 — no channel count needs to be a multiple of
+ * anything —, (C0 + C1) H W < 2^30 and out_channels_total H W < 2^30, any B, H, W >= 1.  `out` must not overlap
+ * an input, and `workspace` no tensor (RMD_ERR_ARG).  `workspace` holds rmd_conv2d_workspace_bytes() bytes
+ * (0 = unsupported arguments) = the packed weights (ceil(Cout / 32) 32 x kh kw x ceil((C0 + C1) / 16) 16
+ * elements x 2 parts x 2 bytes) + 256: the call first repacks the weights into it as MFMA A fragments, so it
+ * may be reused by the next call on the same stream.  The summation order of an output is fixed and does not
+ * depend on the batch, the other tiles or out_offset: bitwise reproducible, per-sample independent.
+ *
+ * rmd_motion_encoder runs BasicMotionEncoder.forward: flow (B, 2, H, W), corr (B, corr_planes, H, W) ->
+ * out (B, 128, H, W); weights / biases are host arrays of five device pointers in the order convc1
+ * (256, corr_planes, 1, 1), convc2 (192, 256, 3, 3), convf1 (128, 2, 7, 7), convf2 (64, 128, 3, 3), conv
+ * (126, 256, 3, 3).  Five launches of the same kernel over one workspace (the five packed weights + the maps
+ * (B, 256, H, W), (B, 128, H, W) and (B, 256, H, W); convc2 and convf2 write channels 0-191 and 192-255 of
+ * the last, conv channels 0-125 of out) and a copy of flow into channels 126-127: no cat, no ReLU pass.
+ * The launchers never allocate, free or synchronise, read no environment variable, and all argument checks
+ * run before any launch.
+ */
+int rmd_conv2d_supported(int kh, int kw, int c0, int c1, int cout);
+size_t rmd_conv2d_workspace_bytes(int c0, int c1, int cout, int kh, int kw);
+int rmd_conv2d(const float* in0, const float* in1, const float* weight, const float* bias, float* out,
+               void* workspace, int batch, int c0, int c1, int cout, int kh, int kw, int height, int width,
+               int out_channels_total, int out_offset, int act, int compute, void* stream);
+size_t rmd_motion_encoder_workspace_bytes(int batch, int corr_planes, int height, int width);
+int rmd_motion_encoder(const float* flow, const float* corr, const float* const* weights, const float* const* biases,
+                       float* out, void* workspace, int batch, int corr_planes, int height, int width, int compute,
+                       void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

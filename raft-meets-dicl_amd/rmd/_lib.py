@@ -125,6 +125,11 @@ _SIGS = {
     "rmd_sepconv_gru_workspace_bytes": (ctypes.c_size_t, [_I] * 5),
     "rmd_sepconv_gru": (_I, [_P] * 6 + [_I] * 6 + [_P]),
     "rmd_sepconv_gru_half": (_I, [_P] * 6 + [_I] * 7 + [_P]),
+    "rmd_conv2d_supported": (_I, [_I] * 5),
+    "rmd_conv2d_workspace_bytes": (ctypes.c_size_t, [_I] * 5),
+    "rmd_conv2d": (_I, [_P] * 6 + [_I] * 12 + [_P]),
+    "rmd_motion_encoder_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
+    "rmd_motion_encoder": (_I, [_P] * 6 + [_I] * 5 + [_P]),
     "rmd_local_cross_attn_kernel":(ctypes.c_char_p, [_I] * 9),
     "rmd_local_cross_attn": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P]),
     "rmd_local_cross_attn_workspace_bytes": (ctypes.c_size_t, [_I] * 5),

@@ -23,8 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_gru_args, check_head_args, check_loss_args,
-                      check_match_args, check_match_backward_args, check_metric_args,
+from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_conv_args, check_encoder_args, check_gru_args,
+                      check_head_args, check_loss_args, check_match_args, check_match_backward_args, check_metric_args,
                       pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
 
@@ -601,6 +601,29 @@ def sepconv_gru(h, x, weights, biases, compute):
     return h
 
 
+# ---- fused k x k convolutions (raft.py:193-225, 262-273, 299-331) ------------------------------------
+
+def conv2d_act(x0, x1, weight, bias, act, compute):
+    """F.conv2d over cat(x0, x1) with 'same' padding, then the activation; fp32 whatever the compute mode."""
+    _, _, _, kh, kw = check_conv_args(x0, x1, weight, bias, act, compute)
+    x = x0.detach().float() if x1 is None else torch.cat([x0.detach().float(), x1.detach().float()], dim=1)
+    out = F.conv2d(x, weight.detach().float(), bias.detach().float().reshape(-1), padding=(kh // 2, kw // 2))
+    return F.relu(out) if act else out
+
+
+def motion_encoder(flow, corr, weights, biases, compute):
+    """BasicMotionEncoder.forward (raft.py:214-225), the reference's own composition in fp32."""
+    check_encoder_args(flow, corr, weights, biases, compute)
+    flow, corr = flow.detach().float(), corr.detach().float()
+    ws, bs = [t.detach().float() for t in weights], [t.detach().float().reshape(-1) for t in biases]
+    cor = F.relu(F.conv2d(corr, ws[0], bs[0]))
+    cor = F.relu(F.conv2d(cor, ws[1], bs[1], padding=1))
+    flo = F.relu(F.conv2d(flow, ws[2], bs[2], padding=3))
+    flo = F.relu(F.conv2d(flo, ws[3], bs[3], padding=1))
+    combined = F.relu(F.conv2d(torch.cat([cor, flo], dim=1), ws[4], bs[4], padding=1))
+    return torch.cat([combined, flow], dim=1)
+
+
 # ---- registration ------------------------------------------------------------------------------
 #
 # The CPU kernel of an operator is the function of its name in this module.
@@ -610,5 +633,5 @@ assert all(_KERNELS.values()), f"every rmd operator needs a CPU kernel: {[n for 
 
 for _name, _fn in _KERNELS.items():
     LIB.impl(_name, _fn, "CPU")
-    if _name not in ("flow_metrics", "dicl_match_1x1", "sepconv_gru"):     # not differentiable: library.py's Autograd kernel serves every device
+    if _name not in ("flow_metrics", "dicl_match_1x1", "sepconv_gru", "conv2d_act", "motion_encoder"):     # not differentiable: library.py's Autograd kernel serves every device
         LIB.impl(_name, _fn, "AutogradCPU")

@@ -29,6 +29,8 @@ follow SURVEY.md §8(b):
   dicl_match_1x1_train(fmap1, fmap2, coords, radius, weights[], biases[])    the same cost (fp32 mode), differentiable:
         / dicl_match_1x1_backward(grad, ..., needs_grad) -> grads[]          its formula recomputes from the inputs
   sepconv_gru(h, x, weights[], biases[], compute) -> (B, Hd, H, W)           raft.py:228-259 (inference)
+  conv2d_act(x0, x1?, weight, bias, act, compute) -> (B, Cout, H, W)         raft.py:193-225, 262-273, 299-331
+  motion_encoder(flow, corr, weights[], biases[], compute) -> (B, 128, H, W) raft.py:193-225 (both inference)
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -46,9 +48,9 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head", "attn", "match", "match_train" and "update" are listed by
+# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update" and "conv" are listed by
 # loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
-# match_train_operators() and update_operators().
+# match_train_operators(), update_operators() and conv_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -94,6 +96,8 @@ _OPS = {
     "dicl_match_1x1_backward": ("match_train", "(Tensor grad, Tensor fmap1, Tensor fmap2, Tensor coords, int radius, "
                                                "Tensor[] weights, Tensor[] biases, bool[] needs_grad) -> Tensor[]"),
     "sepconv_gru": ("update", "(Tensor h, Tensor x, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
+    "conv2d_act": ("conv", "(Tensor x0, Tensor? x1, Tensor weight, Tensor bias, int act, int compute) -> Tensor"),
+    "motion_encoder": ("conv", "(Tensor flow, Tensor corr, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
 }
 for _name, (_, _schema) in _OPS.items():
     LIB.define(_name + _schema)
@@ -141,6 +145,11 @@ def match_train_operators():
 def update_operators():
     """Names of the registered torch.ops.rmd update-block (recurrent unit) operators."""
     return _family("update")
+
+
+def conv_operators():
+    """Names of the registered torch.ops.rmd update-block convolution operators."""
+    return _family("conv")
 
 
 def _hip(name):
@@ -1356,3 +1365,148 @@ def _sepconv_gru_below_autograd(h, x, weights, biases, compute):
 
 
 LIB.impl("sepconv_gru", _sepconv_gru_below_autograd, "Autograd")
+
+
+# ---- fused k x k convolutions (raft.py:193-225, 262-273, 299-331), inference -------------------------
+#
+# conv2d_act: a stride-1, "same"-padded convolution over cat(x0, x1) with bias and activation (act 0: none,
+# 1: ReLU).  motion_encoder: BasicMotionEncoder.forward, parameters in the order convc1, convc2, convf1, convf2,
+# conv.  Not differentiable, like sepconv_gru: training keeps the modules' eager paths.
+
+CONV_COMPUTE = GRU_COMPUTE
+CONV_ACTS = (0, 1)
+CONV_MAX_IMAGE = 1 << 30    # channels H W per image, inputs and destination: 32-bit lane offsets inside an image
+# (Cout, Cin (None: corr_planes), k) of the encoder's five convolutions
+ENCODER_CONVS = ((256, None, 1), (192, 256, 3), (128, 2, 7), (64, 128, 3), (126, 256, 3))
+
+
+def check_conv_args(x0, x1, weight, bias, act, compute):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of conv2d_act; returns
+    (C0, C1, Cout, kh, kw)."""
+    if x0.dim() != 4 or min(x0.shape) < 1:
+        raise ValueError(f"conv2d_act: x0 (B, C0, H, W), not empty, expected, got {tuple(x0.shape)}")
+    c0, c1 = x0.shape[1], 0
+    if x1 is not None:
+        if x1.dim() != 4 or x1.shape[0] != x0.shape[0] or x1.shape[2:] != x0.shape[2:] or x1.shape[1] < 1:
+            raise ValueError(f"conv2d_act: x1 must be (B, C1 >= 1, H, W) like x0 {tuple(x0.shape)}, got "
+                             f"{tuple(x1.shape)}")
+        c1 = x1.shape[1]
+    if compute not in CONV_COMPUTE:
+        raise ValueError(f"conv2d_act: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    if act not in CONV_ACTS:
+        raise ValueError(f"conv2d_act: act {act} (supported: 0 = none, 1 = ReLU)")
+    if weight.dim() != 4 or weight.shape[1] != c0 + c1 or weight.shape[0] < 1:
+        raise ValueError(f"conv2d_act: weight must be (Cout, {c0 + c1}, kh, kw) for inputs of {c0} + {c1} channels, "
+                         f"got {tuple(weight.shape)}")
+    cout, _, kh, kw = weight.shape
+    if kh % 2 != 1 or kw % 2 != 1:
+        raise ValueError(f"conv2d_act: kernel sides must be odd ('same' padding), got {kh} x {kw}")
+    if bias.numel() != cout:
+        raise ValueError(f"conv2d_act: bias must hold {cout} elements, got {tuple(bias.shape)}")
+    for t in (x0, x1, weight, bias):
+        if t is not None and not t.is_floating_point():
+            raise ValueError(f"conv2d_act: tensors must be floating point, got {t.dtype}")
+    return c0, c1, cout, kh, kw
+
+
+def conv_supported(kh, kw, c0, c1, cout):
+    """rmd_conv2d_supported: whether the HIP kernel serves this convolution (host only)."""
+    return bool(_lib.lib().rmd_conv2d_supported(kh, kw, c0, c1, cout))
+
+
+CONV_RANGE = "kernel sides odd in 1..7, C0 + C1 <= 512, Cout <= 1024, channels x H x W < 2^30"
+
+
+def conv_unsupported_reason(kh, kw, c0, c1, cout, ht, wd, out_channels=None):
+    """Why the HIP kernel cannot serve this convolution on an (ht, wd) map (None if it can)."""
+    # the documented range first: what it refuses is refused without the library
+    if kh % 2 != 1 or kw % 2 != 1 or max(kh, kw) > 7 or c0 + c1 > 512 or cout > 1024 \
+            or not conv_supported(kh, kw, c0, c1, cout):
+        return f"unsupported convolution {kh}x{kw}, {c0} + {c1} -> {cout} channels ({CONV_RANGE})"
+    if max(c0 + c1, out_channels or cout) * ht * wd >= CONV_MAX_IMAGE:
+        return f"unsupported size: channels x H x W = {max(c0 + c1, out_channels or cout) * ht * wd} >= 2^30"
+    return None
+
+
+@_hip("conv2d_act")
+def _conv2d_act(x0, x1, weight, bias, act, compute):
+    c0, c1, cout, kh, kw = check_conv_args(x0, x1, weight, bias, act, compute)
+    b, _, ht, wd = x0.shape
+    reason = conv_unsupported_reason(kh, kw, c0, c1, cout, ht, wd)
+    if reason:
+        raise ValueError(f"conv2d_act: unsupported on the GPU: {reason}")
+    a0, a1 = _f32(x0), (None if x1 is None else _f32(x1))
+    wt, bs = _f32(weight), _f32(bias)
+    work = _lib.workspace("conv2d", a0, c0, c1, cout, kh, kw)
+    out = _like(a0, (b, cout, ht, wd))
+    _lib.launch("rmd_conv2d", a0, a0, a1, wt, bs, out, work, b, c0, c1, cout, kh, kw, ht, wd, cout, 0, act, compute)
+    return out
+
+
+@_fake("conv2d_act")
+def _(x0, x1, weight, bias, act, compute):
+    _, _, cout, _, _ = check_conv_args(x0, x1, weight, bias, act, compute)
+    return _like(x0, (x0.shape[0], cout, x0.shape[2], x0.shape[3]))
+
+
+def check_encoder_args(flow, corr, weights, biases, compute):
+    """The shared checks of motion_encoder; returns corr_planes."""
+    if flow.dim() != 4 or corr.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != corr.shape[0] \
+            or flow.shape[2:] != corr.shape[2:] or min(flow.shape) < 1 or corr.shape[1] < 1:
+        raise ValueError(f"motion_encoder: flow (B, 2, H, W) and corr (B, planes, H, W) expected, got "
+                         f"{tuple(flow.shape)} / {tuple(corr.shape)}")
+    if len(weights) != 5 or len(biases) != 5:
+        raise ValueError(f"motion_encoder: need 5 weights and 5 biases, got {len(weights)} and {len(biases)}")
+    if compute not in CONV_COMPUTE:
+        raise ValueError(f"motion_encoder: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    planes = corr.shape[1]
+    for i, ((cout, cin, k), wt, bs) in enumerate(zip(ENCODER_CONVS, weights, biases)):
+        want = (cout, planes if cin is None else cin, k, k)
+        if tuple(wt.shape) != want:
+            raise ValueError(f"motion_encoder: weights[{i}] must be {want}, got {tuple(wt.shape)}")
+        if bs.numel() != cout:
+            raise ValueError(f"motion_encoder: biases[{i}] must hold {cout} elements, got {tuple(bs.shape)}")
+    for t in (flow, corr, *weights, *biases):
+        if not t.is_floating_point():
+            raise ValueError(f"motion_encoder: tensors must be floating point, got {t.dtype}")
+    return planes
+
+
+def encoder_unsupported_reason(planes, ht, wd):
+    """Why the HIP kernels cannot serve the encoder on an (ht, wd) map (None if they can)."""
+    return conv_unsupported_reason(1, 1, planes, 0, 256, ht, wd)
+
+
+@_hip("motion_encoder")
+def _motion_encoder(flow, corr, weights, biases, compute):
+    planes = check_encoder_args(flow, corr, weights, biases, compute)
+    b, _, ht, wd = flow.shape
+    reason = encoder_unsupported_reason(planes, ht, wd)
+    if reason:
+        raise ValueError(f"motion_encoder: unsupported on the GPU: {reason}")
+    fl, co = _f32(flow), _f32(corr)
+    ws, ts = [_f32(t) for t in weights], [_f32(t) for t in biases]
+    work = _lib.workspace("motion_encoder", fl, b, planes, ht, wd)
+    out = _like(fl, (b, 128, ht, wd))
+    _lib.launch("rmd_motion_encoder", fl, fl, co, _pointers(ws), _pointers(ts), out, work, b, planes, ht, wd, compute)
+    return out
+
+
+@_fake("motion_encoder")
+def _(flow, corr, weights, biases, compute):
+    check_encoder_args(flow, corr, weights, biases, compute)
+    return _like(flow, (flow.shape[0], 128, flow.shape[2], flow.shape[3]))
+
+
+def _conv2d_act_below_autograd(x0, x1, weight, bias, act, compute):
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.rmd.conv2d_act(x0, x1, weight, bias, act, compute)
+
+
+def _motion_encoder_below_autograd(flow, corr, weights, biases, compute):
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.rmd.motion_encoder(flow, corr, weights, biases, compute)
+
+
+LIB.impl("conv2d_act", _conv2d_act_below_autograd, "Autograd")
+LIB.impl("motion_encoder", _motion_encoder_below_autograd, "Autograd")

@@ -497,6 +497,34 @@ def sepconv_gru(h, x, weights, biases, precision="fp32"):
     return torch.ops.rmd.sepconv_gru(h, x, weights, biases, GRU_PRECISIONS[precision])
 
 
+CONV_PRECISIONS = MATCH_PRECISIONS
+CONV_ACTS = {"none": 0, "relu": 1}
+
+
+def conv2d_act(x0, x1, weight, bias, act="none", precision="fp32"):
+    """Fused convolution (torch.ops.rmd.conv2d_act; raft.py:193-225, 262-273, 299-331), inference only: a stride-1,
+    "same"-padded convolution over cat(x0 (B, C0, H, W), x1 (B, C1, H, W) or None) with weight (Cout, C0 + C1,
+    kh, kw), kh and kw odd, bias (Cout,) and act "none" or "relu" -> (B, Cout, H, W).  precision "fp32": three
+    split-bf16 products (parity mode); "bf16": one.  Not differentiable."""
+    if precision not in CONV_PRECISIONS:
+        raise ValueError(f"conv2d_act: unknown precision '{precision}', expected one of {sorted(CONV_PRECISIONS)}")
+    if act not in CONV_ACTS:
+        raise ValueError(f"conv2d_act: unknown activation '{act}', expected one of {sorted(CONV_ACTS)}")
+    _same_device(x0, *([] if x1 is None else [x1]), weight, bias)
+    return torch.ops.rmd.conv2d_act(x0, x1, weight, bias, CONV_ACTS[act], CONV_PRECISIONS[precision])
+
+
+def motion_encoder(flow, corr, weights, biases, precision="fp32"):
+    """Fused BasicMotionEncoder (torch.ops.rmd.motion_encoder; raft.py:193-225), inference only: flow (B, 2, H, W),
+    corr (B, planes, H, W), weights and biases of convc1, convc2, convf1, convf2, conv -> (B, 128, H, W) whose
+    last two channels are flow.  Five convolutions with ReLU epilogues; no cat.  Not differentiable."""
+    if precision not in CONV_PRECISIONS:
+        raise ValueError(f"motion_encoder: unknown precision '{precision}', expected one of {sorted(CONV_PRECISIONS)}")
+    weights, biases = list(weights), list(biases)
+    _same_device(flow, corr, *weights, *biases)
+    return torch.ops.rmd.motion_encoder(flow, corr, weights, biases, CONV_PRECISIONS[precision])
+
+
 def dicl_stack_int(fmap1, fmap2, ru, rv):
     """Integer-displacement matching volume with occlusion mask (torch.ops.rmd.dicl_stack_int;
     impls/dicl.py:212-238)."""

@@ -1,11 +1,11 @@
 """Drop-ins for RAFT's update block — qzed/raft-meets-dicl src/models/impls/raft.py:193-296.
 
 BasicMotionEncoder, SepConvGru, FlowHead and BasicUpdateBlock with the reference's constructor arguments,
-attribute names and state-dict keys.  The encoder and the flow head are the reference's plain torch
-modules.  SepConvGru keeps the reference's composition as its default (``fused="off"``) and, in inference,
-can run the whole unit as the fused HIP operator torch.ops.rmd.sepconv_gru (csrc/gru.hip): six MFMA
-implicit-GEMM convolutions with the sigmoid / tanh / gating in their epilogues, no cat, no pre-activation
-in memory.
+attribute names and state-dict keys.  Each keeps the reference's composition as its default (``fused="off"``)
+and, in inference, can run on the fused HIP operators.  SepConvGru: torch.ops.rmd.sepconv_gru (csrc/gru.hip),
+six MFMA implicit-GEMM convolutions with the sigmoid / tanh / gating in their epilogues, no cat, no
+pre-activation in memory.  BasicMotionEncoder: torch.ops.rmd.motion_encoder (csrc/conv.hip), its five
+convolutions with ReLU epilogues writing channel slices, no cat.  FlowHead: two torch.ops.rmd.conv2d_act.
 
 ``fused``:
   "off"   the reference's composition line for line (bitwise the reference's on the CPU); trains.
@@ -15,8 +15,8 @@ in memory.
   "on"    as "auto", but a RuntimeError naming the reason where "auto" would fall back.
 ``precision`` is the operator's: "fp32" (three split-bf16 products, the parity mode) or "bf16" (one).
 
-Forward hooks on the six inner convolutions do not fire on the fused path (they are never called); hooks on
-the unit itself and on the update block do.
+Forward hooks on the inner convolutions (and FlowHead's relu) do not fire on the fused paths (they are never
+called); hooks on the modules themselves and on the update block do.
 """
 
 import torch
@@ -28,11 +28,46 @@ from . import library, ops
 FUSED_MODES = ("off", "auto", "on")
 
 
+def check_fused_arguments(name, fused, precision):
+    if fused not in FUSED_MODES:
+        raise ValueError(f"{name}: unknown fused mode '{fused}', expected one of {FUSED_MODES}")
+    if precision not in ops.CONV_PRECISIONS:
+        raise ValueError(f"{name}: unknown precision '{precision}', expected one of {sorted(ops.CONV_PRECISIONS)}")
+
+
+def conv_fallback_reason(inputs, convs):
+    """Why the fused convolution operators cannot serve `inputs` (4-D maps of one size) through the Conv2d modules
+    `convs` (None if they can): the conditions SepConvGru.fallback_reason documents."""
+    tensors = list(inputs) + [p for c in convs for p in (c.weight, c.bias)]
+    first = inputs[0]
+    if any(t.device != first.device for t in tensors):
+        return "the inputs and the parameters are on different devices"
+    if any(t.dtype != torch.float32 for t in tensors):
+        return "the tensors are not all float32"
+    if torch.is_autocast_enabled() or (first.device.type == "cpu" and torch.is_autocast_enabled("cpu")):
+        return "autocast is on"
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return "a gradient is needed (the fused convolutions are inference only)"
+    if any(t.dim() != 4 for t in inputs):
+        return f"the inputs must be 4-D, got {[tuple(t.shape) for t in inputs]}"
+    if first.is_cuda:
+        for c in convs:
+            kh, kw = c.kernel_size
+            reason = library.conv_unsupported_reason(kh, kw, c.in_channels, 0, c.out_channels, first.shape[2],
+                                                     first.shape[3])
+            if reason:
+                return reason
+    return None
+
+
 class BasicMotionEncoder(nn.Module):
     """Encoder to combine correlation and flow for GRU input (raft.py:193-225)"""
 
-    def __init__(self, corr_planes):
+    def __init__(self, corr_planes, fused="off", precision="fp32"):
         super().__init__()
+        check_fused_arguments("BasicMotionEncoder", fused, precision)
+        self.fused = fused
+        self.precision = precision
 
         self.convc1 = nn.Conv2d(corr_planes, 256, 1, padding=0)
         self.convc2 = nn.Conv2d(256, 192, 3, padding=1)
@@ -44,7 +79,23 @@ class BasicMotionEncoder(nn.Module):
 
         self.output_dim = 128                           # (128 - 2) + 2
 
+    def _convs(self):
+        return (self.convc1, self.convc2, self.convf1, self.convf2, self.conv)
+
+    def fallback_reason(self, flow, corr):
+        """Why the fused operator cannot serve this call (None if it can)."""
+        return conv_fallback_reason([flow, corr], self._convs())
+
     def forward(self, flow, corr):
+        if self.fused != "off":
+            reason = self.fallback_reason(flow, corr)
+            if reason is None:
+                convs = self._convs()
+                return ops.motion_encoder(flow, corr, [c.weight for c in convs], [c.bias for c in convs],
+                                          self.precision)
+            if self.fused == "on":
+                raise RuntimeError(f"BasicMotionEncoder(fused='on'): {reason}")
+
         cor = F.relu(self.convc1(corr))
         cor = F.relu(self.convc2(cor))
 
@@ -134,14 +185,29 @@ class SepConvGru(nn.Module):
 class FlowHead(nn.Module):
     """Head to compute delta-flow from GRU hidden-state (raft.py:262-273)"""
 
-    def __init__(self, input_dim=128, hidden_dim=256, relu_inplace=True):
+    def __init__(self, input_dim=128, hidden_dim=256, relu_inplace=True, fused="off", precision="fp32"):
         super().__init__()
+        check_fused_arguments("FlowHead", fused, precision)
+        self.fused = fused
+        self.precision = precision
 
         self.conv1 = nn.Conv2d(input_dim, hidden_dim, 3, padding=1)
         self.conv2 = nn.Conv2d(hidden_dim, 2, 3, padding=1)
         self.relu = nn.ReLU(inplace=relu_inplace)
 
+    def fallback_reason(self, x):
+        """Why the fused operator cannot serve this call (None if it can)."""
+        return conv_fallback_reason([x], (self.conv1, self.conv2))
+
     def forward(self, x):
+        if self.fused != "off":
+            reason = self.fallback_reason(x)
+            if reason is None:
+                y = ops.conv2d_act(x, None, self.conv1.weight, self.conv1.bias, "relu", self.precision)
+                return ops.conv2d_act(y, None, self.conv2.weight, self.conv2.bias, "none", self.precision)
+            if self.fused == "on":
+                raise RuntimeError(f"FlowHead(fused='on'): {reason}")
+
         return self.conv2(self.relu(self.conv1(x)))
 
 
@@ -149,13 +215,14 @@ class BasicUpdateBlock(nn.Module):
     """Network to compute single flow update delta (raft.py:276-296)"""
 
     def __init__(self, corr_planes, input_dim=128, hidden_dim=128, relu_inplace=True, *, gru_fused="off",
-                 gru_precision="fp32"):
+                 gru_precision="fp32", fused="off", precision="fp32"):
         super().__init__()
 
-        self.enc = BasicMotionEncoder(corr_planes)
+        self.enc = BasicMotionEncoder(corr_planes, fused=fused, precision=precision)
         self.gru = SepConvGru(hidden_dim=hidden_dim, input_dim=input_dim+self.enc.output_dim, fused=gru_fused,
                               precision=gru_precision)
-        self.flow = FlowHead(input_dim=hidden_dim, hidden_dim=256, relu_inplace=relu_inplace)
+        self.flow = FlowHead(input_dim=hidden_dim, hidden_dim=256, relu_inplace=relu_inplace, fused=fused,
+                             precision=precision)
 
     def forward(self, h, x, corr, flow):
         m = self.enc(flow, corr)            # motion features
