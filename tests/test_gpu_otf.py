@@ -87,7 +87,7 @@ def test_otf_matches_oracle(case, precision):
 
 @pytest.mark.parametrize("precision", ["fp32", "fp32-exact", "bf16"])
 def test_otf_wide_box_per_query_path(precision):
-    """Flow scattered over a 600-pixel-wide map: union boxes wider than kMaxT take the per-query path."""
+    """Flow scattered over a 600-pixel-wide map: union boxes wider than kMaxTasks take the per-query path."""
     import rmd
     rng = np.random.default_rng(9)
     b, c, h, w = 1, 24, 4, 600

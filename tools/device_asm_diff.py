@@ -2,7 +2,7 @@
 """Prove that a refactor leaves the compiled kernels unchanged: device assembly of REV against this tree,
 kernel by kernel, so a kernel may move to another source.
 
-    python tools/device_asm_diff.py REV [--rename OLD=NEW ...]
+    python tools/device_asm_diff.py REV [--rename OLD=NEW ...] [--rename-re PATTERN=REPL ...]
 
 Extracts REV's raft-meets-dicl_amd/csrc and include into a temporary directory and builds the device assembly
 of every .hip source there and here (csrc/Makefile's build/asm/%.s rule, this tree's Makefile for both).  Every
@@ -21,6 +21,11 @@ same name, and fall into one class each:
 
 --rename OLD=NEW (repeatable) replaces the mangled name OLD by NEW throughout REV's assembly before the functions
 are matched, so a kernel whose symbol changed (it lost a template parameter, say) is still compared body for body.
+--rename-re PATTERN=REPL does the same with a regular expression (re.sub), for a whole family of instantiations:
+
+    --rename-re '(otf_lookup_kernelI(?:DF16b|f)Lb[01]ELi\\d+ELi\\d+E)Li1E=\\1'
+
+drops the fifth template argument, a constant 1, from every otf_lookup_kernel instantiation.
 
 Prints the counts per source of this tree (REV's source for a missing one) and names every function that is not
 identical.  Exit status 1 unless all are identical or reordered.  Needs hipcc, no GPU.
@@ -109,11 +114,13 @@ def classify(a, b):
 
 def main():
     args, renames = sys.argv[1:], []
-    while "--rename" in args[:-1]:
-        i = args.index("--rename")
-        renames.append(args[i + 1].split("=", 1))
-        del args[i:i + 2]
-    if len(args) != 1 or args[0].startswith("-") or any(len(r) != 2 for r in renames):
+    for flag, literal in (("--rename", True), ("--rename-re", False)):
+        while flag in args[:-1]:
+            i = args.index(flag)
+            was, _, now = args[i + 1].partition("=")
+            renames.append((re.escape(was), now.replace("\\", r"\\")) if literal else (was, now))
+            del args[i:i + 2]
+    if len(args) != 1 or args[0].startswith("-") or not all(was and now for was, now in renames):
         sys.exit(__doc__)
     rev = args[0]
     with tempfile.TemporaryDirectory() as tmp:
@@ -122,7 +129,7 @@ def main():
         subprocess.run(["tar", "-x", "-C", tmp], input=archive, check=True)
         asm = build_asm(pathlib.Path(tmp) / CSRC)
     for was, now in renames:
-        asm = {n: [l.replace(was, now) for l in lines] for n, lines in asm.items()}
+        asm = {n: [re.sub(was, now, l) for l in lines] for n, lines in asm.items()}
     old = collect(asm)
     new = collect(build_asm(ROOT / CSRC))
     # a name keyed with its source on one side only (it was unique there) is keyed alike on both

@@ -3,7 +3,8 @@
 (CPU only): per query block of QSX x QSY 16-query segments and level, the box of its queries' windows
 clipped to the map and widened to 16-target segments; every (box target segment, query segment) pair is
 one 16x16 MFMA tile of C = 256 channels.  Compared with the algorithmic work (each query's in-map
-(2r+2)^2 window).  usage: python tools/otf_work_model.py"""
+(2r+2)^2 window).  The kernel's blocks are one segment wide (QSX = 1); the 32-wide rows are the model's only.
+usage: python tools/otf_work_model.py"""
 import os
 import sys
 
