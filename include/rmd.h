@@ -765,6 +765,67 @@ int rmd_motion_encoder(const float* flow, const float* corr, const float* const*
                        float* out, void* workspace, int batch, int corr_planes, int height, int width, int compute,
                        void* stream);
 
+/*
+ * RAFT's feature / context encoder, inference only: FeatureEncoder (common/encoders/raft/s3.py:8-72) and its
+ * ResidualBlock (common/blocks/raft.py:13-46) for the norm types 'none' and 'instance' (eval-mode batch norm
+ * arrives folded into the weights and biases: norm none).  All maps float32 NCHW.
+ *
+ * rmd_conv2d_strided is rmd_conv2d's MFMA implicit GEMM (same compute modes, same NaN / inf behaviour) over one
+ * map with a stride, an optional transform on load and an optional residual:
+ *   in'[b, c, p]    = scale ? relu(in[b, c, p] scale[b, c] + shift[b, c]) : in[b, c, p]     (fp32, NaN kept)
+ *   v               = act(bias[o] + sum_{c,i,j} W[o, c, i, j] in'[b, c, s y + i - kh/2, s x + j - kw/2])
+ *   out[b, o, y, x] = residual ? relu(v + residual[b, o, y, x]) : v
+ * in (B, C, H, W), weight (Cout, C, kh, kw), out and residual (B, Cout, (H - 1) / s + 1, (W - 1) / s + 1),
+ * scale and shift (B, C), both or neither.  Positions outside the map read zero — the padding of the transformed
+ * map, not relu(shift).  Supported (rmd_conv2d_strided_supported, host only; RMD_ERR_SHAPE otherwise): kh, kw
+ * odd in 1..7, stride 1 or 2, C in 1..512, Cout in 1..1024, C H W < 2^30 and Cout Ho Wo < 2^30.  `workspace`
+ * holds rmd_conv2d_strided_workspace_bytes() bytes (the packed weights + 256), as rmd_conv2d's.
+ *
+ * rmd_instance_stats gives nn.InstanceNorm2d (no affine, no running statistics) in scale / shift form: for every
+ * plane (b, c) of x (B, C, H, W), scale = 1 / sqrt(var + eps) with the biased variance and shift = -mean scale,
+ * so that norm(x) = x scale + shift.  Mean, then centred squares, accumulated in float64 in a fixed order by one
+ * workgroup per plane: no atomics, bitwise reproducible, per-sample independent.  H W = 1 is RMD_ERR_SHAPE
+ * (the reference raises there as well).
+ *
+ * rmd_residual_join: out = relu(xs + relu(ys)), ys = y or y y_scale + y_shift, xs = x or x x_scale + x_shift
+ * (the projection's norm, no ReLU); y, x, out (B, C, H, W), the statistics (B, C), a scale with its shift.
+ *
+ * rmd_feature_encoder runs FeatureEncoder.forward: x (B, 3, H, W) -> out (B, output_dim, H8, W8) with
+ * H2 = (H - 1) / 2 + 1, H4 and H8 likewise.  weights / biases are host arrays of 16 device pointers in module
+ * order: conv1 (64, 3, 7, 7); per ResidualBlock conv1, conv2 and, in the first block of layer2 and layer3,
+ * downsample.0; conv2 (output_dim, 128, 1, 1).  norm = RMD_NORM_NONE: per block the projection if present, conv1
+ * with ReLU, conv2 with the ReLU-and-residual epilogue.  norm = RMD_NORM_INSTANCE (eps as nn.InstanceNorm2d's):
+ * conv1 raw, its statistics, conv2 normalising on load, its statistics, the same two steps for the projection,
+ * the join.  One workspace of rmd_feature_encoder_workspace_bytes() bytes (0 = unsupported arguments): the 16
+ * packed weights, six (B, 128) statistics vectors, three maps that every block's input and two results rotate
+ * through — B max(64 H2 W2, 96 H4 W4, 128 H8 W8) floats each: the first term wherever the sides still halve, but a
+ * side of 1 stays 1 — and one of B max(96 H4 W4, 128 H8 W8) floats for both projections;
+ * rmd_feature_encoder_workspace_regions() writes the four sizes (all packed weights, one statistics vector, one
+ * map, the projection map; bytes, host only) to regions[0..3].  Supported
+ * (rmd_feature_encoder_supported, host only): output_dim in 1..1024, the two norms; with the instance norm
+ * H8 W8 > 1.  The launchers never allocate, free or synchronise, read no environment variable, and all argument
+ * checks (null pointers, overlaps, the 32-bit offset limits) run before any launch.
+ */
+#define RMD_NORM_NONE 0
+#define RMD_NORM_INSTANCE 1
+int rmd_conv2d_strided_supported(int kh, int kw, int stride, int c, int cout);
+size_t rmd_conv2d_strided_workspace_bytes(int c, int cout, int kh, int kw);
+int rmd_conv2d_strided(const float* in, const float* scale, const float* shift, const float* weight,
+                       const float* bias, const float* residual, float* out, void* workspace, int batch, int c,
+                       int cout, int kh, int kw, int height, int width, int stride, int act, int compute,
+                       void* stream);
+int rmd_instance_stats(const float* x, float* scale, float* shift, int batch, int channels, int height, int width,
+                       float eps, void* stream);
+int rmd_residual_join(const float* y, const float* y_scale, const float* y_shift, const float* x,
+                      const float* x_scale, const float* x_shift, float* out, int batch, int channels, int height,
+                      int width, void* stream);
+int rmd_feature_encoder_supported(int output_dim, int norm);
+size_t rmd_feature_encoder_workspace_bytes(int batch, int height, int width, int output_dim);
+int rmd_feature_encoder_workspace_regions(int batch, int height, int width, int output_dim, size_t* regions);
+int rmd_feature_encoder(const float* x, const float* const* weights, const float* const* biases, float* out,
+                        void* workspace, int batch, int height, int width, int output_dim, int norm, float eps,
+                        int compute, void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

@@ -10,6 +10,10 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
   rmd.corr.make_cmod / CorrelationModule <- src/models/common/corr/{dicl,dicl_1x1,dicl_emb,dot}.py
   rmd.raft_dicl_ml.CorrelationModule    <- src/models/impls/raft_dicl_ml.py:235-343
   rmd.blocks.dicl                       <- src/models/common/blocks/dicl.py:93-150
+  rmd.blocks.raft.ResidualBlock         <- src/models/common/blocks/raft.py:13-46
+  rmd.encoders.FeatureEncoder / make_encoder_s3
+                                        <- src/models/common/encoders/raft/s3.py:8-72, encoders/__init__.py:52-60
+                                           (one fused forward, rmd.ops.feature_encoder)
   rmd.dicl.compute_cost                 <- src/models/impls/dicl.py:171-241 (+ fused warp)
   rmd.dicl.FlowRegression / FlowEntropy / FlowLevelMixin
                                         <- src/models/impls/dicl.py:31-85, 186-210 (one fused head pass,
@@ -28,7 +32,7 @@ algorithm), so the modules also run on device='cpu' as the reference's do.
                                            (one fused statistics pass, rmd.ops.flow_metrics)
 """
 
-from . import blocks, config, corr, cpu, dicl, heads, hsup, input, loss, metrics, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
+from . import blocks, config, corr, cpu, dicl, encoders, heads, hsup, input, loss, metrics, ops, raft, raft_dicl_ml, raft_fs, warp  # noqa: F401
 from .hsup import HUpBilinear, HUpCrossAttn, HUpNone, make_hidden_state_upsampler  # noqa: F401
 from .loss import MultiLevelSequenceLoss, MultiscaleLoss, RestrictedMultiLevelSequenceLoss, SequenceLoss  # noqa: F401
 from .metrics import FlowMetrics  # noqa: F401

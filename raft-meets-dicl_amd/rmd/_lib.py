@@ -15,6 +15,7 @@ import torch  # noqa: F401  (load torch's libamdhip64 first so librmd.so binds t
 RMD_OK = 0
 RMD_F32, RMD_F16, RMD_BF16, RMD_BF16X3, RMD_S24 = 0, 1, 2, 3, 4
 RMD_LAYOUT_ROWS, RMD_LAYOUT_TILES = 0, 1
+RMD_NORM_NONE, RMD_NORM_INSTANCE = 0, 1
 MAX_LEVELS = 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +131,15 @@ _SIGS = {
     "rmd_conv2d": (_I, [_P] * 6 + [_I] * 12 + [_P]),
     "rmd_motion_encoder_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
     "rmd_motion_encoder": (_I, [_P] * 6 + [_I] * 5 + [_P]),
+    "rmd_conv2d_strided_supported": (_I, [_I] * 5),
+    "rmd_conv2d_strided_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
+    "rmd_conv2d_strided": (_I, [_P] * 8 + [_I] * 10 + [_P]),
+    "rmd_instance_stats": (_I, [_P] * 3 + [_I] * 4 + [ctypes.c_float, _P]),
+    "rmd_residual_join": (_I, [_P] * 7 + [_I] * 4 + [_P]),
+    "rmd_feature_encoder_supported": (_I, [_I] * 2),
+    "rmd_feature_encoder_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
+    "rmd_feature_encoder_workspace_regions": (_I, [_I] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "rmd_feature_encoder": (_I, [_P] * 5 + [_I] * 5 + [ctypes.c_float, _I, _P]),
     "rmd_local_cross_attn_kernel":(ctypes.c_char_p, [_I] * 9),
     "rmd_local_cross_attn": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P]),
     "rmd_local_cross_attn_workspace_bytes": (ctypes.c_size_t, [_I] * 5),

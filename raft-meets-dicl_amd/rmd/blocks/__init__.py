@@ -1,1 +1,1 @@
-from . import dicl  # noqa: F401
+from . import dicl, raft  # noqa: F401

@@ -23,7 +23,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (LIB, _OPS, _STORAGE, check_attn_args, check_conv_args, check_encoder_args, check_gru_args,
+from .library import (INSTANCE_NORM_EPS, LIB, _OPS, _STORAGE, check_attn_args, check_conv_args, check_encoder_args,
+                      check_feature_encoder_args, check_gru_args, check_join_args, check_norm_conv_args,
+                      check_stats_args,
                       check_head_args, check_loss_args, check_match_args, check_match_backward_args, check_metric_args,
                       pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
@@ -624,6 +626,67 @@ def motion_encoder(flow, corr, weights, biases, compute):
     return torch.cat([combined, flow], dim=1)
 
 
+# ---- the feature / context encoder (encoders/raft/s3.py:8-72, blocks/raft.py:13-46) -------------------
+
+def _planes(t):
+    return t.detach().float()[:, :, None, None]
+
+
+def conv2d_norm_act(x, scale, shift, weight, bias, residual, stride, act, compute):
+    """F.conv2d with padding k / 2 over relu(x scale + shift), the activation, then relu(. + residual); fp32
+    whatever the compute mode."""
+    check_norm_conv_args(x, scale, shift, weight, bias, residual, stride, act, compute)
+    _, _, kh, kw = weight.shape
+    x = x.detach().float()
+    if scale is not None:
+        x = F.relu(x * _planes(scale) + _planes(shift))
+    out = F.conv2d(x, weight.detach().float(), bias.detach().float().reshape(-1), stride=stride,
+                   padding=(kh // 2, kw // 2))
+    out = F.relu(out) if act else out
+    return out if residual is None else F.relu(out + residual.detach().float())
+
+
+def instance_norm_stats(x, eps):
+    """scale = 1 / sqrt(var + eps) (biased variance) and shift = -mean scale per (sample, channel); the moments in
+    float64, as the HIP kernel accumulates them."""
+    check_stats_args(x, eps)
+    var, mean = torch.var_mean(x.detach().double(), dim=(2, 3), unbiased=False)
+    scale = torch.rsqrt(var + eps)
+    return scale.float(), (-mean * scale).float()
+
+
+def residual_join(y, y_scale, y_shift, x, x_scale, x_shift):
+    """relu(xs + relu(ys)), ys = y y_scale + y_shift, xs = x x_scale + x_shift (each as given without statistics)."""
+    check_join_args(y, y_scale, y_shift, x, x_scale, x_shift)
+    y, x = y.detach().float(), x.detach().float()
+    if y_scale is not None:
+        y = y * _planes(y_scale) + _planes(y_shift)
+    if x_scale is not None:
+        x = x * _planes(x_scale) + _planes(x_shift)
+    return F.relu(x + F.relu(y))
+
+
+def feature_encoder(x, weights, biases, norm, compute):
+    """FeatureEncoder.forward (s3.py:51-72) with the norm type none or instance, the reference's own composition
+    in fp32."""
+    check_feature_encoder_args(x, weights, biases, norm, compute)
+    ws, bs = [t.detach().float() for t in weights], [t.detach().float().reshape(-1) for t in biases]
+
+    def nrm(t):
+        return F.instance_norm(t, eps=INSTANCE_NORM_EPS) if norm else t
+
+    x = F.relu(nrm(F.conv2d(x.detach().float(), ws[0], bs[0], stride=2, padding=3)))
+    g = 1
+    for stride in (1, 1, 2, 1, 2, 1):
+        y = F.relu(nrm(F.conv2d(x, ws[g], bs[g], stride=stride, padding=1)))
+        y = F.relu(nrm(F.conv2d(y, ws[g + 1], bs[g + 1], padding=1)))
+        if stride == 2:
+            x = nrm(F.conv2d(x, ws[g + 2], bs[g + 2], stride=2))
+        x = F.relu(x + y)
+        g += 3 if stride == 2 else 2
+    return F.conv2d(x, ws[15], bs[15])
+
+
 # ---- registration ------------------------------------------------------------------------------
 #
 # The CPU kernel of an operator is the function of its name in this module.
@@ -633,5 +696,6 @@ assert all(_KERNELS.values()), f"every rmd operator needs a CPU kernel: {[n for 
 
 for _name, _fn in _KERNELS.items():
     LIB.impl(_name, _fn, "CPU")
-    if _name not in ("flow_metrics", "dicl_match_1x1", "sepconv_gru", "conv2d_act", "motion_encoder"):     # not differentiable: library.py's Autograd kernel serves every device
+    if _name not in ("flow_metrics", "dicl_match_1x1", "sepconv_gru", "conv2d_act", "motion_encoder",
+                     "conv2d_norm_act", "instance_norm_stats", "residual_join", "feature_encoder"):     # not differentiable: library.py's Autograd kernel serves every device
         LIB.impl(_name, _fn, "AutogradCPU")

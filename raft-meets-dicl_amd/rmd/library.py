@@ -31,6 +31,8 @@ follow SURVEY.md §8(b):
   sepconv_gru(h, x, weights[], biases[], compute) -> (B, Hd, H, W)           raft.py:228-259 (inference)
   conv2d_act(x0, x1?, weight, bias, act, compute) -> (B, Cout, H, W)         raft.py:193-225, 262-273, 299-331
   motion_encoder(flow, corr, weights[], biases[], compute) -> (B, 128, H, W) raft.py:193-225 (both inference)
+  conv2d_norm_act / instance_norm_stats / residual_join / feature_encoder     encoders/raft/s3.py:8-72,
+                                                                              blocks/raft.py:13-46 (inference)
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -48,9 +50,9 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update" and "conv" are listed by
-# loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
-# match_train_operators(), update_operators() and conv_operators().
+# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update", "conv" and "encoder" are
+# listed by loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
+# match_train_operators(), update_operators(), conv_operators() and encoder_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -98,6 +100,12 @@ _OPS = {
     "sepconv_gru": ("update", "(Tensor h, Tensor x, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
     "conv2d_act": ("conv", "(Tensor x0, Tensor? x1, Tensor weight, Tensor bias, int act, int compute) -> Tensor"),
     "motion_encoder": ("conv", "(Tensor flow, Tensor corr, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
+    "conv2d_norm_act": ("encoder", "(Tensor x, Tensor? scale, Tensor? shift, Tensor weight, Tensor bias, "
+                                   "Tensor? residual, int stride, int act, int compute) -> Tensor"),
+    "instance_norm_stats": ("encoder", "(Tensor x, float eps) -> (Tensor, Tensor)"),
+    "residual_join": ("encoder", "(Tensor y, Tensor? y_scale, Tensor? y_shift, Tensor x, Tensor? x_scale, "
+                                 "Tensor? x_shift) -> Tensor"),
+    "feature_encoder": ("encoder", "(Tensor x, Tensor[] weights, Tensor[] biases, int norm, int compute) -> Tensor"),
 }
 for _name, (_, _schema) in _OPS.items():
     LIB.define(_name + _schema)
@@ -150,6 +158,11 @@ def update_operators():
 def conv_operators():
     """Names of the registered torch.ops.rmd update-block convolution operators."""
     return _family("conv")
+
+
+def encoder_operators():
+    """Names of the registered torch.ops.rmd feature / context encoder operators."""
+    return _family("encoder")
 
 
 def _hip(name):
@@ -1510,3 +1523,248 @@ def _motion_encoder_below_autograd(flow, corr, weights, biases, compute):
 
 LIB.impl("conv2d_act", _conv2d_act_below_autograd, "Autograd")
 LIB.impl("motion_encoder", _motion_encoder_below_autograd, "Autograd")
+
+
+# ---- the feature / context encoder (encoders/raft/s3.py:8-72, blocks/raft.py:13-46), inference ------------
+#
+# conv2d_norm_act: a convolution of stride 1 or 2 with padding k / 2 over relu(x scale + shift) (x itself without the
+# statistics), bias, activation and, with a residual, relu(. + residual).  instance_norm_stats: nn.InstanceNorm2d at
+# its defaults as (scale, shift), norm(x) = x scale + shift.  residual_join: relu(xs + relu(ys)).  feature_encoder:
+# FeatureEncoder.forward, the 16 convolutions' parameters in module order, norm 0 (none; batch norm folded) or 1
+# (instance).  Not differentiable, like conv2d_act.
+
+ENCODER_STRIDES = (1, 2)
+ENCODER_NORMS = (_lib.RMD_NORM_NONE, _lib.RMD_NORM_INSTANCE)
+INSTANCE_NORM_EPS = 1e-5            # nn.InstanceNorm2d's default, the one feature_encoder uses
+ENCODER_RANGE = "kernel sides odd in 1..7, stride 1 or 2, C <= 512, Cout <= 1024, channels x H x W < 2^30"
+
+
+def out_side(n, stride):
+    """Output side of a convolution of padding k / 2 and this stride over n positions."""
+    return (n - 1) // stride + 1
+
+
+def feature_encoder_convs(output_dim):
+    """(Cout, Cin, k, stride) of FeatureEncoder's 16 convolutions in module order: conv1; per block conv1, conv2
+    and (stride 2) downsample.0; conv2."""
+    convs, cin = [(64, 3, 7, 2)], 64
+    for width, stride in ((64, 1), (96, 2), (128, 2)):
+        convs += [(width, cin, 3, stride), (width, width, 3, 1)]
+        if stride == 2:
+            convs.append((width, cin, 1, 2))
+        convs += [(width, width, 3, 1), (width, width, 3, 1)]
+        cin = width
+    return convs + [(output_dim, 128, 1, 1)]
+
+
+def _check_stats(name, scale, shift, like, what):
+    if (scale is None) != (shift is None):
+        raise ValueError(f"{name}: {what}_scale and {what}_shift are given together")
+    for t in (scale, shift):
+        if t is not None and (tuple(t.shape) != tuple(like.shape[:2]) or not t.is_floating_point()):
+            raise ValueError(f"{name}: the statistics of {what} must be floating point (B, C) = "
+                             f"{tuple(like.shape[:2])}, got {tuple(t.shape)} {t.dtype}")
+
+
+def check_norm_conv_args(x, scale, shift, weight, bias, residual, stride, act, compute):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of conv2d_norm_act; returns the
+    output's shape."""
+    name = "conv2d_norm_act"
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{name}: x (B, C, H, W), not empty, expected, got {tuple(x.shape)}")
+    if compute not in CONV_COMPUTE:
+        raise ValueError(f"{name}: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    if act not in CONV_ACTS:
+        raise ValueError(f"{name}: act {act} (supported: 0 = none, 1 = ReLU)")
+    if stride not in ENCODER_STRIDES:
+        raise ValueError(f"{name}: stride {stride} (supported: 1, 2)")
+    b, c, ht, wd = x.shape
+    if weight.dim() != 4 or weight.shape[1] != c or weight.shape[0] < 1:
+        raise ValueError(f"{name}: weight must be (Cout, {c}, kh, kw), got {tuple(weight.shape)}")
+    cout, _, kh, kw = weight.shape
+    if kh % 2 != 1 or kw % 2 != 1:
+        raise ValueError(f"{name}: kernel sides must be odd (padding k / 2), got {kh} x {kw}")
+    if bias.numel() != cout:
+        raise ValueError(f"{name}: bias must hold {cout} elements, got {tuple(bias.shape)}")
+    _check_stats(name, scale, shift, x, "x")
+    shape = (b, cout, out_side(ht, stride), out_side(wd, stride))
+    if residual is not None and tuple(residual.shape) != shape:
+        raise ValueError(f"{name}: residual must be {shape}, got {tuple(residual.shape)}")
+    for t in (x, weight, bias, residual):
+        if t is not None and not t.is_floating_point():
+            raise ValueError(f"{name}: tensors must be floating point, got {t.dtype}")
+    return shape
+
+
+def norm_conv_unsupported_reason(kh, kw, stride, c, cout, ht, wd):
+    """Why the HIP kernel cannot serve this convolution on an (ht, wd) map (None if it can)."""
+    # the documented range first: what it refuses is refused without the library
+    if kh % 2 != 1 or kw % 2 != 1 or max(kh, kw) > 7 or stride not in ENCODER_STRIDES or c > 512 or cout > 1024 \
+            or not _lib.lib().rmd_conv2d_strided_supported(kh, kw, stride, c, cout):
+        return f"unsupported convolution {kh}x{kw} stride {stride}, {c} -> {cout} channels ({ENCODER_RANGE})"
+    size = max(c * ht * wd, cout * out_side(ht, stride) * out_side(wd, stride))
+    if size >= CONV_MAX_IMAGE:
+        return f"unsupported size: channels x H x W = {size} >= 2^30"
+    return None
+
+
+def _opt(t):
+    return None if t is None else _f32(t)
+
+
+@_hip("conv2d_norm_act")
+def _conv2d_norm_act(x, scale, shift, weight, bias, residual, stride, act, compute):
+    shape = check_norm_conv_args(x, scale, shift, weight, bias, residual, stride, act, compute)
+    b, c, ht, wd = x.shape
+    cout, _, kh, kw = weight.shape
+    reason = norm_conv_unsupported_reason(kh, kw, stride, c, cout, ht, wd)
+    if reason:
+        raise ValueError(f"conv2d_norm_act: unsupported on the GPU: {reason}")
+    xx, wt, bs = _f32(x), _f32(weight), _f32(bias)
+    work = _lib.workspace("conv2d_strided", xx, c, cout, kh, kw)
+    out = _like(xx, shape)
+    _lib.launch("rmd_conv2d_strided", xx, xx, _opt(scale), _opt(shift), wt, bs, _opt(residual), out, work, b, c, cout,
+                kh, kw, ht, wd, stride, act, compute)
+    return out
+
+
+@_fake("conv2d_norm_act")
+def _(x, scale, shift, weight, bias, residual, stride, act, compute):
+    return _like(x, check_norm_conv_args(x, scale, shift, weight, bias, residual, stride, act, compute))
+
+
+def check_stats_args(x, eps):
+    """The shared checks of instance_norm_stats."""
+    if x.dim() != 4 or min(x.shape) < 1 or not x.is_floating_point():
+        raise ValueError(f"instance_norm_stats: floating point x (B, C, H, W), not empty, expected, got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    if x.shape[2] * x.shape[3] < 2:
+        raise ValueError(f"instance_norm_stats: a plane of one pixel has no variance, got {tuple(x.shape)}")
+    if not eps >= 0:
+        raise ValueError(f"instance_norm_stats: eps must not be negative, got {eps}")
+
+
+@_hip("instance_norm_stats")
+def _instance_norm_stats(x, eps):
+    check_stats_args(x, eps)
+    b, c, ht, wd = x.shape
+    if ht * wd >= CONV_MAX_IMAGE:
+        raise ValueError(f"instance_norm_stats: unsupported on the GPU: H x W = {ht * wd} >= 2^30")
+    xx = _f32(x)
+    scale, shift = _like(xx, (b, c)), _like(xx, (b, c))
+    _lib.launch("rmd_instance_stats", xx, xx, scale, shift, b, c, ht, wd, ctypes.c_float(eps))
+    return scale, shift
+
+
+@_fake("instance_norm_stats")
+def _(x, eps):
+    check_stats_args(x, eps)
+    return _like(x, x.shape[:2]), _like(x, x.shape[:2])
+
+
+def check_join_args(y, y_scale, y_shift, x, x_scale, x_shift):
+    """The shared checks of residual_join."""
+    if y.dim() != 4 or min(y.shape) < 1 or x.shape != y.shape:
+        raise ValueError(f"residual_join: y and x (B, C, H, W), not empty, of one shape expected, got "
+                         f"{tuple(y.shape)} / {tuple(x.shape)}")
+    if not (y.is_floating_point() and x.is_floating_point()):
+        raise ValueError(f"residual_join: tensors must be floating point, got {y.dtype} / {x.dtype}")
+    _check_stats("residual_join", y_scale, y_shift, y, "y")
+    _check_stats("residual_join", x_scale, x_shift, x, "x")
+
+
+@_hip("residual_join")
+def _residual_join(y, y_scale, y_shift, x, x_scale, x_shift):
+    check_join_args(y, y_scale, y_shift, x, x_scale, x_shift)
+    b, c, ht, wd = y.shape
+    if ht * wd >= CONV_MAX_IMAGE:
+        raise ValueError(f"residual_join: unsupported on the GPU: H x W = {ht * wd} >= 2^30")
+    yy, xx = _f32(y), _f32(x)
+    out = _like(yy)
+    _lib.launch("rmd_residual_join", yy, yy, _opt(y_scale), _opt(y_shift), xx, _opt(x_scale), _opt(x_shift), out, b, c,
+                ht, wd)
+    return out
+
+
+@_fake("residual_join")
+def _(y, y_scale, y_shift, x, x_scale, x_shift):
+    check_join_args(y, y_scale, y_shift, x, x_scale, x_shift)
+    return _like(y)
+
+
+def check_feature_encoder_args(x, weights, biases, norm, compute):
+    """The shared checks of feature_encoder; returns the output's shape."""
+    name = "feature_encoder"
+    if x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1:
+        raise ValueError(f"{name}: x (B, 3, H, W), not empty, expected, got {tuple(x.shape)}")
+    if len(weights) != 16 or len(biases) != 16:
+        raise ValueError(f"{name}: need 16 weights and 16 biases, got {len(weights)} and {len(biases)}")
+    if compute not in CONV_COMPUTE:
+        raise ValueError(f"{name}: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    if norm not in ENCODER_NORMS:
+        raise ValueError(f"{name}: norm {norm} (supported: RMD_NORM_NONE = 0, RMD_NORM_INSTANCE = 1)")
+    if weights[15].dim() != 4 or weights[15].shape[0] < 1:
+        raise ValueError(f"{name}: weights[15] must be (output_dim, 128, 1, 1), got {tuple(weights[15].shape)}")
+    output_dim = weights[15].shape[0]
+    for i, ((cout, cin, k, _), wt, bs) in enumerate(zip(feature_encoder_convs(output_dim), weights, biases)):
+        if tuple(wt.shape) != (cout, cin, k, k):
+            raise ValueError(f"{name}: weights[{i}] must be {(cout, cin, k, k)}, got {tuple(wt.shape)}")
+        if bs.numel() != cout:
+            raise ValueError(f"{name}: biases[{i}] must hold {cout} elements, got {tuple(bs.shape)}")
+    for t in (x, *weights, *biases):
+        if not t.is_floating_point():
+            raise ValueError(f"{name}: tensors must be floating point, got {t.dtype}")
+    ht, wd = x.shape[2:]
+    for _ in range(3):
+        ht, wd = out_side(ht, 2), out_side(wd, 2)
+    if norm == _lib.RMD_NORM_INSTANCE and ht * wd < 2:
+        raise ValueError(f"{name}: the instance norm needs more than one pixel at 1/8 resolution, got an input of "
+                         f"{tuple(x.shape[2:])}")
+    return (x.shape[0], output_dim, ht, wd)
+
+
+def feature_encoder_unsupported_reason(output_dim, ht, wd):
+    """Why the HIP kernels cannot serve the encoder on an (ht, wd) image (None if they can)."""
+    if output_dim > 1024:
+        return f"unsupported output_dim {output_dim} (at most 1024)"
+    size, h, w = 0, ht, wd
+    for width in (64, 96, 128):         # a side of 1 stays 1 while the channels grow: the largest map is not always the first
+        h, w = out_side(h, 2), out_side(w, 2)
+        size = max(size, width * h * w)
+    if max(size, 3 * ht * wd, output_dim * h * w) >= CONV_MAX_IMAGE:
+        return f"unsupported size: channels x H x W = {max(size, 3 * ht * wd, output_dim * h * w)} >= 2^30"
+    return None
+
+
+@_hip("feature_encoder")
+def _feature_encoder(x, weights, biases, norm, compute):
+    shape = check_feature_encoder_args(x, weights, biases, norm, compute)
+    b, _, ht, wd = x.shape
+    reason = feature_encoder_unsupported_reason(shape[1], ht, wd)
+    if reason:
+        raise ValueError(f"feature_encoder: unsupported on the GPU: {reason}")
+    xx = _f32(x)
+    ws, ts = [_f32(t) for t in weights], [_f32(t) for t in biases]
+    work = _lib.workspace("feature_encoder", xx, b, ht, wd, shape[1])
+    out = _like(xx, shape)
+    _lib.launch("rmd_feature_encoder", xx, xx, _pointers(ws), _pointers(ts), out, work, b, ht, wd, shape[1], norm,
+                ctypes.c_float(INSTANCE_NORM_EPS), compute)
+    return out
+
+
+@_fake("feature_encoder")
+def _(x, weights, biases, norm, compute):
+    return _like(x, check_feature_encoder_args(x, weights, biases, norm, compute))
+
+
+def _below_autograd(name):
+    op = getattr(torch.ops.rmd, name)
+
+    def kernel(*args):
+        with torch._C._AutoDispatchBelowAutograd():
+            return op(*args)
+    LIB.impl(name, kernel, "Autograd")
+
+
+for _name in _family("encoder"):
+    _below_autograd(_name)

@@ -525,6 +525,56 @@ def motion_encoder(flow, corr, weights, biases, precision="fp32"):
     return torch.ops.rmd.motion_encoder(flow, corr, weights, biases, CONV_PRECISIONS[precision])
 
 
+ENCODER_NORMS = {"none": _lib.RMD_NORM_NONE, "instance": _lib.RMD_NORM_INSTANCE}
+
+
+def _given(*tensors):
+    return [t for t in tensors if t is not None]
+
+
+def conv2d_norm_act(x, weight, bias, scale=None, shift=None, residual=None, stride=1, act="none", precision="fp32"):
+    """Strided, normalising convolution (torch.ops.rmd.conv2d_norm_act; blocks/raft.py:13-46), inference only: a
+    convolution of stride 1 or 2 and padding k / 2 over relu(x scale + shift) (the (B, C) statistics of
+    instance_norm_stats; x itself without them), bias, act "none" or "relu" and, with a residual of the output's
+    shape, relu(. + residual) -> (B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1).  Not differentiable."""
+    if precision not in CONV_PRECISIONS:
+        raise ValueError(f"conv2d_norm_act: unknown precision '{precision}', expected one of {sorted(CONV_PRECISIONS)}")
+    if act not in CONV_ACTS:
+        raise ValueError(f"conv2d_norm_act: unknown activation '{act}', expected one of {sorted(CONV_ACTS)}")
+    _same_device(x, weight, bias, *_given(scale, shift, residual))
+    return torch.ops.rmd.conv2d_norm_act(x, scale, shift, weight, bias, residual, stride, CONV_ACTS[act],
+                                         CONV_PRECISIONS[precision])
+
+
+def instance_norm_stats(x, eps=1e-5):
+    """nn.InstanceNorm2d at its defaults in scale / shift form (torch.ops.rmd.instance_norm_stats): x (B, C, H, W)
+    -> (scale, shift), both (B, C), with norm(x) = x scale + shift.  Not differentiable."""
+    _same_device(x)
+    return torch.ops.rmd.instance_norm_stats(x, float(eps))
+
+
+def residual_join(y, x, y_stats=None, x_stats=None):
+    """relu(xs + relu(ys)) (torch.ops.rmd.residual_join; blocks/raft.py:38-46): ys = y scale + shift for y_stats =
+    (scale, shift), xs likewise (the projection's norm); each as given without statistics.  Not differentiable."""
+    ya, yd = y_stats or (None, None)
+    xa, xd = x_stats or (None, None)
+    _same_device(y, x, *_given(ya, yd, xa, xd))
+    return torch.ops.rmd.residual_join(y, ya, yd, x, xa, xd)
+
+
+def feature_encoder(x, weights, biases, norm="none", precision="fp32"):
+    """Fused FeatureEncoder (torch.ops.rmd.feature_encoder; encoders/raft/s3.py:8-72), inference only: x (B, 3, H, W),
+    the 16 convolutions' weights and biases in module order (batch norm folded in), norm "none" or "instance"
+    -> (B, output_dim, H / 8, W / 8).  Not differentiable."""
+    if precision not in CONV_PRECISIONS:
+        raise ValueError(f"feature_encoder: unknown precision '{precision}', expected one of {sorted(CONV_PRECISIONS)}")
+    if norm not in ENCODER_NORMS:
+        raise ValueError(f"feature_encoder: unknown norm '{norm}', expected one of {sorted(ENCODER_NORMS)}")
+    weights, biases = list(weights), list(biases)
+    _same_device(x, *weights, *biases)
+    return torch.ops.rmd.feature_encoder(x, weights, biases, ENCODER_NORMS[norm], CONV_PRECISIONS[precision])
+
+
 def dicl_stack_int(fmap1, fmap2, ru, rv):
     """Integer-displacement matching volume with occlusion mask (torch.ops.rmd.dicl_stack_int;
     impls/dicl.py:212-238)."""
