@@ -826,6 +826,52 @@ int rmd_feature_encoder(const float* x, const float* const* weights, const float
                         void* workspace, int batch, int height, int width, int output_dim, int norm, float eps,
                         int compute, void* stream);
 
+/*
+ * The k x k DICL MatchingNet, inference only: MatchingNet (common/blocks/dicl.py:93-118) — four ConvBlocks
+ * (:15-23; 3 x 3 at stride 1, 2, 1, 1), one ConvBlockTransposed (:26-34; 4 x 4, stride 2, padding 1) and a 3 x 3
+ * convolution with bias to one channel (:108) — for the norm types 'none' and eval-mode 'batch', which arrives
+ * folded into the weights and biases: every block is relu(W' x + t).  All maps float32 NCHW.
+ *
+ * rmd_mnet_tail computes the last two layers in one kernel; the c4-channel map between them never reaches memory:
+ *   u[n, o, Y, X]  = relu(bias5[o] + sum_{c,ky,kx} weight5[c, o, ky, kx] x[n, c, iy, ix])
+ *                    over Y = 2 iy - 1 + ky, X = 2 ix - 1 + kx with (iy, ix) inside the map
+ *   cost[n, Y, X]  = bias6[0] + sum_{o,i,j} weight6[o, i, j] u[n, o, Y + i - 1, X + j - 1], u zero outside the map
+ * x (images, c3, h2, w2), weight5 (c3, c4, 4, 4) in nn.ConvTranspose2d's layout, bias5 c4 floats, weight6 (c4, 3, 3),
+ * bias6 one float on the device, cost (images, 2 h2, 2 w2).  Layer 5 runs as four MFMA implicit GEMMs, one per
+ * output parity class, whose operands pass through bfloat16: compute = RMD_BF16X3 (three split-bf16 products, the
+ * parity mode) or RMD_BF16 (one); bias5 and the ReLU (v < 0 ? 0 : v: NaN stays NaN) are fp32, and layer 6 is fp32
+ * in both modes.  A NaN input gives NaN in exactly the outputs whose receptive field holds it; a +-inf input gives
+ * NaN there in the parity mode (inf - inf in the residual), the one deviation from the reference.  Supported
+ * (rmd_mnet_tail_supported, host only; RMD_ERR_SHAPE otherwise): c3 in 1..64, c4 in 1..32 — neither needs to be a
+ * multiple of anything —, h2, w2 >= 1 with c3 h2 w2 < 2^30, any number of images.  `workspace` holds
+ * rmd_mnet_tail_workspace_bytes() bytes (0 = unsupported arguments) = the packed weights (4 classes x 4 taps x
+ * ceil(c3 / 16) fragments of 1 KiB x 2 parts) + 256: the call first repacks weight5 into it.
+ *
+ * rmd_matching_net runs the whole network: mvol (images, c_in, h, w) — the displacement stack viewed as in
+ * MatchingNet.forward (:111-118) — -> cost (images, h, w).  weights / biases are host arrays of six device
+ * pointers: four (Cout, Cin, 3, 3) weights with their Cout-float biases (c_in -> c1 -> c2 -> c2 -> c3), weight5
+ * and bias5, weight6 and bias6 as above.  Layers 1-4 are rmd_conv2d_strided's kernel with the ReLU epilogue.  All
+ * five weights are packed once per call; then the images are walked in groups of `group` (the last one smaller),
+ * five launches per group, over one workspace of rmd_matching_net_workspace_bytes() bytes (0 = unsupported
+ * arguments): the five packed weights, then one group's four intermediate maps — group c1 h w, group c2 h/2 w/2
+ * twice and group c3 h/2 w/2 floats, each rounded up to 256 bytes — + 256.  A group larger than `images` counts as
+ * `images`.  Supported (rmd_matching_net_supported, host only): h and w even (on odd sides the reference's view
+ * fails), c_in, c1, c2 in 1..512, c3 and c4 as the tail's, channels x H x W < 2^30 for every map.  Every image's
+ * result is independent of the other images and of `group`, bit for bit.  The launchers never allocate, free or
+ * synchronise, read no environment variable, and all argument checks (null pointers, overlaps, group < 1, the
+ * 32-bit offset limits) run before any launch.
+ */
+int rmd_mnet_tail_supported(int c3, int c4, int h2, int w2);
+size_t rmd_mnet_tail_workspace_bytes(int c3, int c4);
+int rmd_mnet_tail(const float* x, const float* weight5, const float* bias5, const float* weight6, const float* bias6,
+                  float* cost, void* workspace, int images, int c3, int c4, int h2, int w2, int compute,
+                  void* stream);
+int rmd_matching_net_supported(int c_in, int c1, int c2, int c3, int c4, int h, int w);
+size_t rmd_matching_net_workspace_bytes(int group, int c_in, int c1, int c2, int c3, int c4, int h, int w);
+int rmd_matching_net(const float* mvol, const float* const* weights, const float* const* biases, float* cost,
+                     void* workspace, int images, int group, int c_in, int c1, int c2, int c3, int c4, int h, int w,
+                     int compute, void* stream);
+
 /* Message for the last failing call on this thread ("" if none). */
 const char* rmd_last_error(void);
 

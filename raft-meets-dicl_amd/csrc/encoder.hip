@@ -36,6 +36,7 @@
 // Every output's summation order is fixed (channel chunk, tap row, tap column, k-step; small products first) and
 // depends on nothing but its own image: results are bitwise repeatable and per-sample independent.
 
+#include "encoder.h"
 #include "mfma_bf16.h"
 
 namespace rmd {
@@ -352,15 +353,8 @@ size_t sconv_packed_bytes(int c, int cout, int kh, int kw) {
     return nfrag * 64 * sizeof(bf16x8) * 2;
 }
 
-// the checks of one convolution of entry point `name`, before any launch
-int sconv_check(const char* name, const float* in, const float* scale, const float* shift, const float* weight,
-                const float* bias, const float* res, const float* out, int batch, int c, int cout, int kh, int kw,
-                int height, int width, int stride, int act, int compute) {
-    RMD_REQUIRE(in && weight && bias && out, RMD_ERR_ARG, "%s: null pointer", name);
-    RMD_REQUIRE((scale == nullptr) == (shift == nullptr), RMD_ERR_ARG, "%s: scale and shift are given together", name);
-    RMD_REQUIRE(compute == RMD_BF16X3 || compute == RMD_BF16, RMD_ERR_ARG,
-                "%s: compute must be RMD_BF16X3 or RMD_BF16, got %d", name, compute);
-    RMD_REQUIRE(act == 0 || act == 1, RMD_ERR_ARG, "%s: act must be 0 (none) or 1 (ReLU), got %d", name, act);
+// the shape checks of one convolution of entry point `name`
+int sconv_shape(const char* name, int batch, int c, int cout, int kh, int kw, int height, int width, int stride) {
     RMD_REQUIRE(batch > 0 && height > 0 && width > 0, RMD_ERR_SHAPE, "%s: bad sizes", name);
     RMD_REQUIRE(sconv_supported(kh, kw, stride, c, cout), RMD_ERR_SHAPE,
                 "%s: unsupported (kernel %dx%d, stride %d, channels %d -> %d): kernel sides odd in 1..7, stride 1 or 2, "
@@ -370,9 +364,24 @@ int sconv_check(const char* name, const float* in, const float* scale, const flo
     // 32-bit lane offsets into one image's maps, 64-bit everywhere else
     RMD_REQUIRE(n * c < (1ll << 30) && no * cout < (1ll << 30), RMD_ERR_SHAPE,
                 "%s: %lld pixels x %d channels in, %lld x %d out per image", name, n, c, no, cout);
-    const SConvGeom P = sconv_geom(batch, c, cout, kh, kw, stride, height, width, act);
+    const SConvGeom P = sconv_geom(batch, c, cout, kh, kw, stride, height, width, 0);
     RMD_REQUIRE((long long)batch * P.tiles_y * P.tiles_x * P.mpass <= 0x7fffffffll, RMD_ERR_SHAPE,
                 "%s: too many pixel tiles (batch=%d height=%d width=%d)", name, batch, height, width);
+    return RMD_OK;
+}
+
+// the checks of one convolution of entry point `name`, before any launch
+int sconv_check(const char* name, const float* in, const float* scale, const float* shift, const float* weight,
+                const float* bias, const float* res, const float* out, int batch, int c, int cout, int kh, int kw,
+                int height, int width, int stride, int act, int compute) {
+    RMD_REQUIRE(in && weight && bias && out, RMD_ERR_ARG, "%s: null pointer", name);
+    RMD_REQUIRE((scale == nullptr) == (shift == nullptr), RMD_ERR_ARG, "%s: scale and shift are given together", name);
+    RMD_REQUIRE(compute == RMD_BF16X3 || compute == RMD_BF16, RMD_ERR_ARG,
+                "%s: compute must be RMD_BF16X3 or RMD_BF16, got %d", name, compute);
+    RMD_REQUIRE(act == 0 || act == 1, RMD_ERR_ARG, "%s: act must be 0 (none) or 1 (ReLU), got %d", name, act);
+    if (int rc = sconv_shape(name, batch, c, cout, kh, kw, height, width, stride)) return rc;
+    const long long n = (long long)height * width;
+    const long long no = (long long)out_side(height, stride) * out_side(width, stride);
     const size_t obytes = (size_t)batch * cout * no * sizeof(float);
     const size_t ibytes = (size_t)batch * c * n * sizeof(float), sbytes = (size_t)batch * c * sizeof(float);
     const size_t wbytes = (size_t)cout * c * kh * kw * sizeof(float);
@@ -403,16 +412,27 @@ void sconv_dispatch(const float* in, const float* scale, const float* shift, con
     else sconv_launch<NP, 4, 16>(in, scale, shift, fr, bias, res, out, P, st);
 }
 
+// packs `weight` at `frags`
+void sconv_pack_run(const float* weight, void* frags, const SConvGeom& P, int compute, hipStream_t st) {
+    const int threads = P.mo * 32 * 2 * P.ks;
+    sconv_pack_kernel<<<(threads + 255) / 256, 256, 0, st>>>(weight, P.Cout, P.C, P.taps, P.mo, P.ks, P.nfrag,
+                                                            compute == RMD_BF16X3 ? 1 : 0,
+                                                            reinterpret_cast<bf16x8*>(frags));
+}
+
+// runs the convolution on the fragments sconv_pack_run wrote for `compute`
+void sconv_packed_run(const float* in, const float* scale, const float* shift, const void* frags, const float* bias,
+                      const float* res, float* out, const SConvGeom& P, int compute, hipStream_t st) {
+    const bf16x8* fr = reinterpret_cast<const bf16x8*>(frags);
+    if (compute == RMD_BF16X3) sconv_dispatch<3>(in, scale, shift, fr, bias, res, out, P, st);
+    else sconv_dispatch<1>(in, scale, shift, fr, bias, res, out, P, st);
+}
+
 // packs `weight` at `frags` and runs the convolution
 void sconv_run(const float* in, const float* scale, const float* shift, const float* weight, const float* bias,
                const float* res, float* out, void* frags, const SConvGeom& P, int compute, hipStream_t st) {
-    const bool lo = compute == RMD_BF16X3;
-    bf16x8* fr = reinterpret_cast<bf16x8*>(frags);
-    const int threads = P.mo * 32 * 2 * P.ks;
-    sconv_pack_kernel<<<(threads + 255) / 256, 256, 0, st>>>(weight, P.Cout, P.C, P.taps, P.mo, P.ks, P.nfrag,
-                                                            lo ? 1 : 0, fr);
-    if (lo) sconv_dispatch<3>(in, scale, shift, fr, bias, res, out, P, st);
-    else sconv_dispatch<1>(in, scale, shift, fr, bias, res, out, P, st);
+    sconv_pack_run(weight, frags, P, compute, st);
+    sconv_packed_run(in, scale, shift, frags, bias, res, out, P, compute, st);
 }
 
 void stats_run(const float* x, int planes, int hw, float eps, float* a, float* d, hipStream_t st) {
@@ -506,6 +526,25 @@ inline bool enc_supported(int output_dim, int norm) {
 }
 
 }  // namespace
+
+// ---- encoder.h: the convolution's two steps for other launchers -------------------------------------------
+
+size_t sconv_frag_bytes(int c, int cout, int kh, int kw) { return sconv_packed_bytes(c, cout, kh, kw); }
+
+int sconv_check_shape(const char* name, int batch, int c, int cout, int kh, int kw, int height, int width, int stride) {
+    return sconv_shape(name, batch, c, cout, kh, kw, height, width, stride);
+}
+
+void sconv_pack(const float* weight, void* frags, int c, int cout, int kh, int kw, int compute, hipStream_t st) {
+    sconv_pack_run(weight, frags, sconv_geom(1, c, cout, kh, kw, 1, 1, 1, 0), compute, st);
+}
+
+void sconv_packed(const float* in, const void* frags, const float* bias, float* out, int batch, int c, int cout, int kh,
+                  int kw, int height, int width, int stride, int act, int compute, hipStream_t st) {
+    sconv_packed_run(in, nullptr, nullptr, frags, bias, nullptr, out,
+                     sconv_geom(batch, c, cout, kh, kw, stride, height, width, act), compute, st);
+}
+
 }  // namespace rmd
 
 using namespace rmd;

@@ -140,6 +140,12 @@ _SIGS = {
     "rmd_feature_encoder_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
     "rmd_feature_encoder_workspace_regions": (_I, [_I] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
     "rmd_feature_encoder": (_I, [_P] * 5 + [_I] * 5 + [ctypes.c_float, _I, _P]),
+    "rmd_mnet_tail_supported": (_I, [_I] * 4),
+    "rmd_mnet_tail_workspace_bytes": (ctypes.c_size_t, [_I] * 2),
+    "rmd_mnet_tail": (_I, [_P] * 7 + [_I] * 6 + [_P]),
+    "rmd_matching_net_supported": (_I, [_I] * 7),
+    "rmd_matching_net_workspace_bytes": (ctypes.c_size_t, [_I] * 8),
+    "rmd_matching_net": (_I, [_P] * 5 + [_I] * 10 + [_P]),
     "rmd_local_cross_attn_kernel":(ctypes.c_char_p, [_I] * 9),
     "rmd_local_cross_attn": (_I, [_P, _P, _P] + [_I] * 9 + [_P, _P]),
     "rmd_local_cross_attn_workspace_bytes": (ctypes.c_size_t, [_I] * 5),

@@ -2,7 +2,7 @@
 
 The grid_sample / expand / cat that build the (B, 2r+1, 2r+1, 2C, h, w) MatchingNet input
 (:36-54) run as one rmd_dicl_stack pass; `mnet` and `dap` stay the reference's modules (names,
-parameters and forward hooks unchanged).
+parameters and forward hooks unchanged).  `fused` and `precision` are MatchingNet's (rmd.blocks.dicl).
 """
 
 import torch
@@ -19,10 +19,11 @@ def _delta(radius):
 
 class CorrelationModule(nn.Module):
     def __init__(self, feature_dim, radius, dap_init="identity", norm_type="batch", relu_inplace=True,
-                 mnet_scale=1):
+                 mnet_scale=1, fused="off", precision="fp32"):
         super().__init__()
         self.radius = radius
-        self.mnet = MatchingNet(2 * feature_dim, norm_type=norm_type, relu_inplace=relu_inplace, scale=mnet_scale)
+        self.mnet = MatchingNet(2 * feature_dim, norm_type=norm_type, relu_inplace=relu_inplace, scale=mnet_scale,
+                                fused=fused, precision=precision)
         self.dap = DisplacementAwareProjection((radius, radius), init=dap_init)
         self.register_buffer("delta", _delta(radius), persistent=False)
         self.output_dim = (2 * self.radius + 1) ** 2

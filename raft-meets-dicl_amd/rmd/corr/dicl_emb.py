@@ -1,7 +1,7 @@
 """Drop-in for corr.dicl_emb.CorrelationModule — src/models/common/corr/dicl_emb.py:32-104.
 
 The stack carries the two displacement channels (dx, dy) after the feature pair (:81-85), written
-by the same rmd_dicl_stack pass (extra_delta).
+by the same rmd_dicl_stack pass (extra_delta).  `fused` and `precision` are MatchingNet's (rmd.blocks.dicl).
 """
 
 import torch
@@ -30,10 +30,11 @@ class PairEmbedding(nn.Sequential):
 
 class CorrelationModule(nn.Module):
     def __init__(self, feature_dim, radius, embedding_dim=32, dap_init="identity", norm_type="batch",
-                 relu_inplace=True):
+                 relu_inplace=True, fused="off", precision="fp32"):
         super().__init__()
         self.radius = radius
-        self.mnet = MatchingNet(2 * feature_dim + 2, norm_type=norm_type, relu_inplace=relu_inplace)
+        self.mnet = MatchingNet(2 * feature_dim + 2, norm_type=norm_type, relu_inplace=relu_inplace, fused=fused,
+                                precision=precision)
         self.emb = PairEmbedding(2 * feature_dim + 2, embedding_dim, relu_inplace=relu_inplace)
         self.dap = DisplacementAwareProjection((radius, radius), init=dap_init)
         self.register_buffer("delta", _delta(radius), persistent=False)

@@ -24,8 +24,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .library import (INSTANCE_NORM_EPS, LIB, _OPS, _STORAGE, check_attn_args, check_conv_args, check_encoder_args,
-                      check_feature_encoder_args, check_gru_args, check_join_args, check_norm_conv_args,
-                      check_stats_args,
+                      check_feature_encoder_args, check_gru_args, check_join_args, check_mnet_args,
+                      check_norm_conv_args, check_stats_args, check_tail_args,
                       check_head_args, check_loss_args, check_match_args, check_match_backward_args, check_metric_args,
                       pyramid_elements, pyramid_layout, pyramid_storage, s24_decode)
 
@@ -687,6 +687,29 @@ def feature_encoder(x, weights, biases, norm, compute):
     return F.conv2d(x, ws[15], bs[15])
 
 
+# ---- the k x k MatchingNet (blocks/dicl.py:93-118) ----------------------------------------------------
+
+def mnet_tail(x, weight5, bias5, weight6, bias6, compute):
+    """relu(conv_transpose2d(x, W5', t5, stride 2, padding 1)), then the 3 x 3 convolution to one channel; fp32
+    whatever the compute mode."""
+    c3, c4 = check_tail_args(x, weight5, bias5, weight6, bias6, compute)
+    u = F.relu(F.conv_transpose2d(x.detach().float(), weight5.detach().float(), bias5.detach().float().reshape(-1),
+                                  stride=2, padding=1))
+    return F.conv2d(u, weight6.detach().float().reshape(1, c4, 3, 3), bias6.detach().float().reshape(-1), padding=1)[:, 0]
+
+
+def matching_net(mvol, weights, biases, group, compute):
+    """MatchingNet.forward (blocks/dicl.py:111-118) on the folded parameters, the reference's own composition in
+    fp32; `group` only sizes the HIP workspace."""
+    check_mnet_args(mvol, weights, biases, group, compute)
+    b, du, dv, c_in, ht, wd = mvol.shape
+    ws, bs = [t.detach().float() for t in weights], [t.detach().float().reshape(-1) for t in biases]
+    x = mvol.detach().float().reshape(b * du * dv, c_in, ht, wd)
+    for i, stride in enumerate((1, 2, 1, 1)):
+        x = F.relu(F.conv2d(x, ws[i], bs[i], stride=stride, padding=1))
+    return mnet_tail(x, ws[4], bs[4], ws[5], bs[5], compute).reshape(b, du, dv, ht, wd)
+
+
 # ---- registration ------------------------------------------------------------------------------
 #
 # The CPU kernel of an operator is the function of its name in this module.
@@ -697,5 +720,6 @@ assert all(_KERNELS.values()), f"every rmd operator needs a CPU kernel: {[n for 
 for _name, _fn in _KERNELS.items():
     LIB.impl(_name, _fn, "CPU")
     if _name not in ("flow_metrics", "dicl_match_1x1", "sepconv_gru", "conv2d_act", "motion_encoder",
-                     "conv2d_norm_act", "instance_norm_stats", "residual_join", "feature_encoder"):     # not differentiable: library.py's Autograd kernel serves every device
+                     "conv2d_norm_act", "instance_norm_stats", "residual_join", "feature_encoder", "matching_net",
+                     "mnet_tail"):     # not differentiable: library.py's Autograd kernel serves every device
         LIB.impl(_name, _fn, "AutogradCPU")

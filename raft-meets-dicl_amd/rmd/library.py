@@ -33,6 +33,8 @@ follow SURVEY.md §8(b):
   motion_encoder(flow, corr, weights[], biases[], compute) -> (B, 128, H, W) raft.py:193-225 (both inference)
   conv2d_norm_act / instance_norm_stats / residual_join / feature_encoder     encoders/raft/s3.py:8-72,
                                                                               blocks/raft.py:13-46 (inference)
+  matching_net(mvol, weights[], biases[], group, compute) -> (B, du, dv, h, w) blocks/dicl.py:93-118 (inference)
+  mnet_tail(x, weight5, bias5, weight6, bias6, compute) -> (N, 2 h2, 2 w2)    its last two layers (:107-108)
 
 The RAFT correlation's training path keeps rmd.ops' token-linked autograd functions: all lookups of
 one CorrBlock accumulate into ONE dense pyramid gradient (query-minor, fp32) whose layout differs from
@@ -50,9 +52,9 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update", "conv" and "encoder" are
-# listed by loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
-# match_train_operators(), update_operators(), conv_operators() and encoder_operators().
+# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update", "conv", "encoder" and "mnet"
+# are listed by loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
+# match_train_operators(), update_operators(), conv_operators(), encoder_operators() and mnet_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -106,6 +108,9 @@ _OPS = {
     "residual_join": ("encoder", "(Tensor y, Tensor? y_scale, Tensor? y_shift, Tensor x, Tensor? x_scale, "
                                  "Tensor? x_shift) -> Tensor"),
     "feature_encoder": ("encoder", "(Tensor x, Tensor[] weights, Tensor[] biases, int norm, int compute) -> Tensor"),
+    "matching_net": ("mnet", "(Tensor mvol, Tensor[] weights, Tensor[] biases, int group, int compute) -> Tensor"),
+    "mnet_tail": ("mnet", "(Tensor x, Tensor weight5, Tensor bias5, Tensor weight6, Tensor bias6, int compute) "
+                          "-> Tensor"),
 }
 for _name, (_, _schema) in _OPS.items():
     LIB.define(_name + _schema)
@@ -163,6 +168,11 @@ def conv_operators():
 def encoder_operators():
     """Names of the registered torch.ops.rmd feature / context encoder operators."""
     return _family("encoder")
+
+
+def mnet_operators():
+    """Names of the registered torch.ops.rmd k x k matching-network operators."""
+    return _family("mnet")
 
 
 def _hip(name):
@@ -1767,4 +1777,138 @@ def _below_autograd(name):
 
 
 for _name in _family("encoder"):
+    _below_autograd(_name)
+
+
+# ---- the k x k MatchingNet (blocks/dicl.py:93-118), inference ---------------------------------------------
+#
+# matching_net: MatchingNet.forward on folded parameters (MatchingNet.folded()): weights [W1' .. W4' (Cout, Cin, 3, 3),
+# W5' (c3, c4, 4, 4) in nn.ConvTranspose2d's layout, w6 (c4, 3, 3)], biases [t1 .. t5, b6 (one element)]; `group` is
+# the number of images (of the B du dv) per pass over the workspace.  mnet_tail: its last two layers on x (N, c3, h2,
+# w2).  Not differentiable, like conv2d_act.
+
+MNET_MAX_IMAGE = CONV_MAX_IMAGE
+MNET_RANGE = ("h and w even, layer inputs of at most 512 channels, c3 <= 64, c4 <= 32, channels x H x W < 2^30 for every "
+              "map")
+
+
+def check_tail_args(x, weight5, bias5, weight6, bias6, compute):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of mnet_tail; returns (c3, c4)."""
+    name = "mnet_tail"
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{name}: x (N, c3, h2, w2), not empty, expected, got {tuple(x.shape)}")
+    if compute not in CONV_COMPUTE:
+        raise ValueError(f"{name}: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    c3 = x.shape[1]
+    if weight5.dim() != 4 or weight5.shape[0] != c3 or weight5.shape[1] < 1 or tuple(weight5.shape[2:]) != (4, 4):
+        raise ValueError(f"{name}: weight5 must be ({c3}, c4, 4, 4), got {tuple(weight5.shape)}")
+    c4 = weight5.shape[1]
+    if bias5.numel() != c4:
+        raise ValueError(f"{name}: bias5 must hold {c4} elements, got {tuple(bias5.shape)}")
+    if tuple(weight6.shape) != (c4, 3, 3):
+        raise ValueError(f"{name}: weight6 must be ({c4}, 3, 3), got {tuple(weight6.shape)}")
+    if bias6.numel() != 1:
+        raise ValueError(f"{name}: bias6 must hold one element, got {tuple(bias6.shape)}")
+    for t in (x, weight5, bias5, weight6, bias6):
+        if not t.is_floating_point():
+            raise ValueError(f"{name}: tensors must be floating point, got {t.dtype}")
+    return c3, c4
+
+
+def tail_supported(c3, c4, h2, w2):
+    """rmd_mnet_tail_supported: whether the HIP kernel serves these sizes (host only)."""
+    return c3 * h2 * w2 < MNET_MAX_IMAGE and bool(_lib.lib().rmd_mnet_tail_supported(c3, c4, h2, w2))
+
+
+@_hip("mnet_tail")
+def _mnet_tail(x, weight5, bias5, weight6, bias6, compute):
+    c3, c4 = check_tail_args(x, weight5, bias5, weight6, bias6, compute)
+    n, _, h2, w2 = x.shape
+    if not tail_supported(c3, c4, h2, w2):
+        raise ValueError(f"mnet_tail: unsupported on the GPU: channels {c3} -> {c4} on {h2} x {w2} (c3 <= 64, c4 <= 32, "
+                         f"c3 h2 w2 < 2^30)")
+    xx, w5, b5, w6, b6 = (_f32(t) for t in (x, weight5, bias5, weight6, bias6))
+    work = _lib.workspace("mnet_tail", xx, c3, c4)
+    out = _like(xx, (n, 2 * h2, 2 * w2))
+    _lib.launch("rmd_mnet_tail", xx, xx, w5, b5, w6, b6, out, work, n, c3, c4, h2, w2, compute)
+    return out
+
+
+@_fake("mnet_tail")
+def _(x, weight5, bias5, weight6, bias6, compute):
+    check_tail_args(x, weight5, bias5, weight6, bias6, compute)
+    return _like(x, (x.shape[0], 2 * x.shape[2], 2 * x.shape[3]))
+
+
+def check_mnet_args(mvol, weights, biases, group, compute):
+    """Shape, dtype and argument checks shared by the GPU, CPU and fake kernels of matching_net; returns the widths
+    (c_in, c1, c2, c3, c4)."""
+    name = "matching_net"
+    if mvol.dim() != 6 or min(mvol.shape) < 1:
+        raise ValueError(f"{name}: mvol (B, du, dv, c_in, h, w), not empty, expected, got {tuple(mvol.shape)}")
+    if len(weights) != 6 or len(biases) != 6:
+        raise ValueError(f"{name}: need 6 weights and 6 biases, got {len(weights)} and {len(biases)}")
+    if compute not in CONV_COMPUTE:
+        raise ValueError(f"{name}: compute {compute} (supported: RMD_BF16X3 = 3, RMD_BF16 = 2)")
+    if group < 1:
+        raise ValueError(f"{name}: group must be at least 1, got {group}")
+    c_in, ht, wd = mvol.shape[3:]
+    if ht % 2 or wd % 2:
+        raise ValueError(f"{name}: h and w must be even (the reference's view fails on odd sides), got {ht} x {wd}")
+    for i in (0, 1, 2, 3):
+        if weights[i].dim() != 4 or weights[i].shape[0] < 1:
+            raise ValueError(f"{name}: weights[{i}] must be (Cout, Cin, 3, 3), got {tuple(weights[i].shape)}")
+    c1, c2, c3 = weights[0].shape[0], weights[1].shape[0], weights[3].shape[0]
+    if weights[4].dim() != 4 or weights[4].shape[1] < 1:
+        raise ValueError(f"{name}: weights[4] must be ({c3}, c4, 4, 4), got {tuple(weights[4].shape)}")
+    c4 = weights[4].shape[1]
+    want = [(c1, c_in, 3, 3), (c2, c1, 3, 3), (c2, c2, 3, 3), (c3, c2, 3, 3), (c3, c4, 4, 4), (c4, 3, 3)]
+    for i, (wt, bs, shape) in enumerate(zip(weights, biases, want)):
+        if tuple(wt.shape) != shape:
+            raise ValueError(f"{name}: weights[{i}] must be {shape}, got {tuple(wt.shape)}")
+        n = 1 if i == 5 else (c4 if i == 4 else shape[0])
+        if bs.numel() != n:
+            raise ValueError(f"{name}: biases[{i}] must hold {n} elements, got {tuple(bs.shape)}")
+    for t in (mvol, *weights, *biases):
+        if not t.is_floating_point():
+            raise ValueError(f"{name}: tensors must be floating point, got {t.dtype}")
+    return c_in, c1, c2, c3, c4
+
+
+def mnet_supported(c_in, c1, c2, c3, c4, ht, wd):
+    """rmd_matching_net_supported: whether the HIP kernels serve these sizes (host only)."""
+    if max(c_in, c1) * ht * wd >= MNET_MAX_IMAGE:      # the documented range first: ints that fit the C call
+        return False
+    return bool(_lib.lib().rmd_matching_net_supported(c_in, c1, c2, c3, c4, ht, wd))
+
+
+def mnet_workspace_bytes(group, c_in, c1, c2, c3, c4, ht, wd):
+    """rmd_matching_net_workspace_bytes (host only; 0: unsupported arguments)."""
+    return _lib.lib().rmd_matching_net_workspace_bytes(group, c_in, c1, c2, c3, c4, ht, wd)
+
+
+@_hip("matching_net")
+def _matching_net(mvol, weights, biases, group, compute):
+    widths = check_mnet_args(mvol, weights, biases, group, compute)
+    b, du, dv, _, ht, wd = mvol.shape
+    if not mnet_supported(*widths, ht, wd):
+        raise ValueError(f"matching_net: unsupported on the GPU: channels {widths} on {ht} x {wd} ({MNET_RANGE})")
+    n = b * du * dv
+    group = min(group, n)
+    xx = _f32(mvol)
+    ws, ts = [_f32(t) for t in weights], [_f32(t) for t in biases]
+    work = _lib.workspace("matching_net", xx, group, *widths, ht, wd)
+    out = _like(xx, (b, du, dv, ht, wd))
+    _lib.launch("rmd_matching_net", xx, xx, _pointers(ws), _pointers(ts), out, work, n, group, *widths, ht, wd, compute)
+    return out
+
+
+@_fake("matching_net")
+def _(mvol, weights, biases, group, compute):
+    check_mnet_args(mvol, weights, biases, group, compute)
+    b, du, dv, _, ht, wd = mvol.shape
+    return _like(mvol, (b, du, dv, ht, wd))
+
+
+for _name in _family("mnet"):
     _below_autograd(_name)

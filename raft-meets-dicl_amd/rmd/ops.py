@@ -575,6 +575,62 @@ def feature_encoder(x, weights, biases, norm="none", precision="fp32"):
     return torch.ops.rmd.feature_encoder(x, weights, biases, ENCODER_NORMS[norm], CONV_PRECISIONS[precision])
 
 
+MNET_PRECISIONS = MATCH_PRECISIONS
+# Default budget of matching_net's workspace (the packed weights and one group's four intermediate maps).
+# Provenance: tools/mnet_probe.py, profiles/mnet_r18.json "budgets" — the whole network at the cfg4 1/8 level on b8
+# (648 images of 64 x 48 x 160; MIOpen 18.5 ms), median of 20, fp32 / bf16 mode:
+#    64 MiB (groups of 12)  20.13 / 11.78 ms
+#   128 MiB (24)            12.84 /  7.86 ms
+#   256 MiB (49)            12.88 /  5.82 ms
+#   512 MiB (98)            13.04 /  5.15 ms
+# The fp32 mode is flat from 128 MiB on (within 1.6 %), the bf16 mode keeps gaining; 512 MiB has the smallest sum of
+# the two and is the default.  No knee at the 256 MiB Infinity Cache shows in either mode.
+MNET_WORKSPACE_BYTES = 512 << 20
+
+
+def mnet_group(images, widths, height, width, workspace_bytes=None):
+    """Images per pass of matching_net: the largest count whose workspace (rmd_matching_net_workspace_bytes) fits
+    `workspace_bytes` (default MNET_WORKSPACE_BYTES), at least 1 and at most `images`.  Host arithmetic only."""
+    budget = MNET_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    one = library.mnet_workspace_bytes(1, *widths, height, width)
+    if one == 0:
+        raise ValueError(f"matching_net: unsupported sizes: channels {tuple(widths)} on {height} x {width} "
+                         f"({library.MNET_RANGE})")
+    per = library.mnet_workspace_bytes(2, *widths, height, width) - one     # the maps are linear in the group
+    group = max(1, min(images, 1 + (budget - one) // per if budget > one else 1))
+    while group > 1 and library.mnet_workspace_bytes(group, *widths, height, width) > budget:
+        group -= 1                                                          # each map is rounded up to 256 bytes
+    return group
+
+
+def matching_net(mvol, weights, biases, precision="fp32", workspace_bytes=None):
+    """Fused k x k MatchingNet (torch.ops.rmd.matching_net; blocks/dicl.py:93-118), inference only: mvol (B, du, dv,
+    c_in, h, w), h and w even, with the folded parameters of MatchingNet.folded() -> cost (B, du, dv, h, w).  The
+    B du dv images are walked in groups whose workspace fits `workspace_bytes` (default MNET_WORKSPACE_BYTES); the
+    result does not depend on it, bit for bit.  precision "fp32": three split-bf16 products per layer (parity mode);
+    "bf16": one; the last layer is fp32 in both.  Not differentiable."""
+    if precision not in MNET_PRECISIONS:
+        raise ValueError(f"matching_net: unknown precision '{precision}', expected one of {sorted(MNET_PRECISIONS)}")
+    weights, biases = list(weights), list(biases)
+    _same_device(mvol, *weights, *biases)
+    group = 1
+    if mvol.device.type == "cuda":
+        widths = library.check_mnet_args(mvol, weights, biases, 1, MNET_PRECISIONS[precision])
+        b, du, dv, _, ht, wd = mvol.shape
+        group = mnet_group(b * du * dv, widths, ht, wd, workspace_bytes)
+    return torch.ops.rmd.matching_net(mvol, weights, biases, group, MNET_PRECISIONS[precision])
+
+
+def mnet_tail(x, weight5, bias5, weight6, bias6, precision="fp32"):
+    """The last two layers of MatchingNet in one kernel (torch.ops.rmd.mnet_tail; blocks/dicl.py:107-108), inference
+    only: x (N, c3, h2, w2), weight5 (c3, c4, 4, 4) and bias5 (c4,) of the transposed convolution (norm folded in),
+    weight6 (c4, 3, 3) and bias6 (1,) -> cost (N, 2 h2, 2 w2).  Not differentiable."""
+    if precision not in MNET_PRECISIONS:
+        raise ValueError(f"mnet_tail: unknown precision '{precision}', expected one of {sorted(MNET_PRECISIONS)}")
+    _same_device(x, weight5, bias5, weight6, bias6)
+    return torch.ops.rmd.mnet_tail(x, weight5, bias5, weight6, bias6, MNET_PRECISIONS[precision])
+
+
 def dicl_stack_int(fmap1, fmap2, ru, rv):
     """Integer-displacement matching volume with occlusion mask (torch.ops.rmd.dicl_stack_int;
     impls/dicl.py:212-238)."""

@@ -31,7 +31,7 @@ class FullDap(nn.Conv2d):
 
 class CorrelationModule(nn.Module):
     def __init__(self, feature_dim, levels, radius, dap_init="identity", dap_type="separate",
-                 norm_type="batch", share=False, relu_inplace=True):
+                 norm_type="batch", share=False, relu_inplace=True, fused="off", precision="fp32"):
         super().__init__()
         if dap_type not in ("full", "separate"):
             raise ValueError(f"DAP type '{dap_type}' not supported")
@@ -40,7 +40,8 @@ class CorrelationModule(nn.Module):
         self.share = share
 
         def mk_mnet():
-            return MatchingNet(2 * feature_dim, norm_type=norm_type, relu_inplace=relu_inplace)
+            return MatchingNet(2 * feature_dim, norm_type=norm_type, relu_inplace=relu_inplace, fused=fused,
+                               precision=precision)
 
         def mk_dap():
             return DisplacementAwareProjection((radius, radius), init=dap_init)
