@@ -137,6 +137,23 @@ int rmd_corr_prepare(const float* fmap1, const float* fmap2, int channels, float
 int rmd_corr_pyramid_prepared(int channels, float scale, const rmd_pyramid_desc* desc, int compute,
                               void* pyramid, void* workspace, void* stream);
 
+/* rmd_corr_pyramid without the target operand's round trip through the workspace.  Where the call runs the w8
+ * GEMM (rmd_corr_gemm_kernel) only fmap1 is converted into the workspace and the GEMM builds its target tiles
+ * from fmap2 (fp32) itself; the pyramid is bit-identical to rmd_corr_pyramid's.  Every other GEMM runs
+ * rmd_corr_pyramid's two halves.  Same arguments, descriptor, workspace size and error codes as rmd_corr_pyramid. */
+int rmd_corr_pyramid_fused(const float* fmap1, const float* fmap2, int channels, float scale,
+                           const rmd_pyramid_desc* desc, int compute, void* pyramid, void* workspace,
+                           void* stream);
+
+/* The two halves of rmd_corr_pyramid_fused's w8 route, for callers that time them separately.  Both return
+ * RMD_ERR_ARG for a null pointer and for arguments another GEMM than w8 serves (after rmd_corr_pyramid's own
+ * checks of desc, channels and compute).  rmd_corr_pyramid_staged reads what rmd_corr_prepare_queries (or
+ * rmd_corr_prepare) left in the workspace for the same arguments. */
+int rmd_corr_prepare_queries(const float* fmap1, int channels, const rmd_pyramid_desc* desc, int compute,
+                             void* workspace, void* stream);
+int rmd_corr_pyramid_staged(const float* fmap2, int channels, float scale, const rmd_pyramid_desc* desc,
+                            int compute, void* pyramid, void* workspace, void* stream);
+
 /*
  * Windowed bilinear pyramid lookup.  Replaces raft.CorrBlock.__call__ (raft.py:49-95):
  * level i is sampled at (x/2^i + a - r, y/2^i + b - r), bilinear, align_corners=True, zero

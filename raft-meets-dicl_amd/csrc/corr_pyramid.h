@@ -47,6 +47,11 @@ bool eligible(const rmd_pyramid_desc& d, int channels);
 int prepare(const float* fmap1, const float* fmap2, int channels, float scale, const rmd_pyramid_desc& d,
             void* workspace, hipStream_t st);
 int pyramid(const rmd_pyramid_desc& d, void* pyramid, void* workspace, hipStream_t st);
+// the same pyramid without the A operand's round trip through the workspace: prepare_queries() writes the B operand
+// only and pyramid_staged() builds its A tiles from fmap2 (fp32) itself
+int prepare_queries(const float* fmap1, int channels, const rmd_pyramid_desc& d, void* workspace, hipStream_t st);
+int pyramid_staged(const float* fmap2, int channels, float scale, const rmd_pyramid_desc& d, void* pyramid,
+                   void* workspace, hipStream_t st);
 
 }  // namespace w8
 

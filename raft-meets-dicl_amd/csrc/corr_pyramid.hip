@@ -21,7 +21,9 @@
 //  * tiled       corr_pyramid_tiled.hip       everything else: compute F32 (exact f32 MFMA, fp32-exact), any C,
 //                                             BF16 with f32 storage, BF16X3 with C > 256 (as F32); rows
 // Each GEMM reads operands that a prep kernel of its own wrote into the caller's workspace (stationary reads
-// tiled's), so rmd_corr_prepare routes the same way.
+// tiled's), so rmd_corr_prepare routes the same way.  rmd_corr_pyramid_fused (the torch operator's entry) differs
+// on w8 only: prep_queries writes the query operand alone and the GEMM stages its targets from fp32 fmap2
+// (rmd_corr_prepare_queries + rmd_corr_pyramid_staged are its halves); the pyramid is bit-identical.
 
 #include "corr_pyramid.h"
 
@@ -127,6 +129,39 @@ extern "C" int rmd_corr_pyramid_prepared(int channels, float scale, const rmd_py
         case rmd::Path::STATIONARY: return rmd::stationary::pyramid(*d, pyramid, workspace, st);
         default: return rmd::tiled::pyramid(channels, scale, *d, rmd::tiled_compute(compute), pyramid, workspace, st);
     }
+}
+
+extern "C" int rmd_corr_prepare_queries(const float* fmap1, int channels, const rmd_pyramid_desc* d, int compute,
+                                        void* workspace, void* stream) {
+    RMD_REQUIRE(fmap1 && workspace, RMD_ERR_ARG, "rmd_corr_prepare_queries: null pointer");
+    int rc = rmd::check_args(d, channels, compute);
+    if (rc) return rc;
+    RMD_REQUIRE(rmd::gemm_path(*d, channels, compute) == rmd::Path::W8, RMD_ERR_ARG,
+                "rmd_corr_prepare_queries: the w8 GEMM only (see rmd_corr_gemm_kernel)");
+    return rmd::w8::prepare_queries(fmap1, channels, *d, workspace, rmd::as_stream(stream));
+}
+
+extern "C" int rmd_corr_pyramid_staged(const float* fmap2, int channels, float scale, const rmd_pyramid_desc* d,
+                                       int compute, void* pyramid, void* workspace, void* stream) {
+    RMD_REQUIRE(fmap2 && pyramid && workspace, RMD_ERR_ARG, "rmd_corr_pyramid_staged: null pointer");
+    int rc = rmd::check_args(d, channels, compute);
+    if (rc) return rc;
+    RMD_REQUIRE(rmd::gemm_path(*d, channels, compute) == rmd::Path::W8, RMD_ERR_ARG,
+                "rmd_corr_pyramid_staged: the w8 GEMM only (see rmd_corr_gemm_kernel)");
+    return rmd::w8::pyramid_staged(fmap2, channels, scale, *d, pyramid, workspace, rmd::as_stream(stream));
+}
+
+extern "C" int rmd_corr_pyramid_fused(const float* fmap1, const float* fmap2, int channels, float scale,
+                                      const rmd_pyramid_desc* d, int compute, void* pyramid, void* workspace,
+                                      void* stream) {
+    RMD_REQUIRE(fmap1 && fmap2 && pyramid && workspace, RMD_ERR_ARG, "rmd_corr_pyramid_fused: null pointer");
+    int rc = rmd::check_args(d, channels, compute);
+    if (rc) return rc;
+    if (rmd::gemm_path(*d, channels, compute) != rmd::Path::W8)
+        return rmd_corr_pyramid(fmap1, fmap2, channels, scale, d, compute, pyramid, workspace, stream);
+    rc = rmd::w8::prepare_queries(fmap1, channels, *d, workspace, rmd::as_stream(stream));
+    if (rc) return rc;
+    return rmd::w8::pyramid_staged(fmap2, channels, scale, *d, pyramid, workspace, rmd::as_stream(stream));
 }
 
 extern "C" int rmd_corr_pyramid(const float* fmap1, const float* fmap2, int channels, float scale,

@@ -1,5 +1,7 @@
 // corr_pyramid_w8.hip — the bf16 correlation GEMM of the performance path (bf16 operands, fp16 pyramid in the
-// tiles layout of rmd.h, C <= 256, 32-bit store offsets) and its operand prep.
+// tiles layout of rmd.h, C <= 256, 32-bit store offsets) and its operand prep, in two forms: corr_pyramid_w8 reads
+// both operands from the workspace (prep_pair), corr_pyramid_w8_f32 only the queries (prep_queries) and builds its
+// target tiles from fp32 fmap2 (stage_a_f32).
 //
 // One workgroup (8 waves, two per SIMD) owns a 16x16 block of level-0 target pixels; its A operand
 // (256 targets x 256 channels bf16) stays in LDS while the waves sweep their own 32-query tiles
@@ -22,7 +24,8 @@
 namespace rmd {
 namespace {
 
-// prep (both operands in one launch): grid (128-element tiles, B, 2).  z = 0: fmap2 ->
+// prep (prep_pair: both operands in one launch, the bf16-staging GEMM's; prep_queries: the B operand alone, the
+// fp32-staging GEMM's): grid (128-element tiles, B, 2).  z = 0: fmap2 ->
 // A operand (B, N, 256) bf16 * scale over raster pixels; z = 1: fmap1 -> B operand over the query
 // slots of the tiles layout (rmd.h), in MFMA B-fragment order
 //   o[b][qt][s][lane][8]  (lane = j + 32h: channels 16s + 8h .. +7 of slot 32 qt + j),
@@ -33,11 +36,11 @@ namespace {
 // block for either operand.  Slots of no pixel take a clamped pixel's features.
 constexpr int kPrepPx = 128, kPrepStride = 256 * 2 + 16;     // LDS row: 256 bf16 + 16 B pad
 
-__global__ void __launch_bounds__(512)
-prep_pair(const float* __restrict__ f1, const float* __restrict__ f2, __bf16* __restrict__ opA,
-          __bf16* __restrict__ opB, int C, int H, int W, int S, int nqt, float scale) {
+// One 128-element tile of operand `which` of image b = blockIdx.y, tile blockIdx.x.
+__device__ __forceinline__ void prep_tile(const int which, const float* f1, const float* f2, __bf16* opA, __bf16* opB,
+                                          int C, int H, int W, int S, int nqt, float scale) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int b = blockIdx.y, which = blockIdx.z;
+    const int b = blockIdx.y;
     const int N = H * W;
     const float* f = which ? f1 : f2;
     const float s = which ? 1.0f : scale;
@@ -110,6 +113,18 @@ prep_pair(const float* __restrict__ f1, const float* __restrict__ f2, __bf16* __
             *reinterpret_cast<bf16x8*>(opA + ((size_t)b * N + p0) * 256 + (size_t)k * 8) = o;
         }
     }
+}
+
+__global__ void __launch_bounds__(512)
+prep_pair(const float* __restrict__ f1, const float* __restrict__ f2, __bf16* __restrict__ opA,
+          __bf16* __restrict__ opB, int C, int H, int W, int S, int nqt, float scale) {
+    prep_tile(blockIdx.z, f1, f2, opA, opB, C, H, W, S, nqt, scale);
+}
+
+// The z = 1 half alone, grid (tiles, B): the fp32-staging GEMM (corr_pyramid_w8_f32) reads fmap2 itself.
+__global__ void __launch_bounds__(512)
+prep_queries(const float* __restrict__ f1, __bf16* __restrict__ opB, int C, int H, int W, int S, int nqt) {
+    prep_tile(1, f1, nullptr, nullptr, opB, C, H, W, S, nqt, 1.0f);
 }
 
 // ---- the pooled epilogue, in 16 pieces -----------------------------------------------------------
@@ -291,6 +306,82 @@ __device__ __forceinline__ void epilogue(const f32x16 (&acc)[8], const Ctx& c, c
     }
 }
 
+// ---- A staging from fp32 -----------------------------------------------------------------------
+// The LDS A image of one workgroup built from fmap2 itself (f2: this image's (C, H, W) fp32) instead of from
+// opA.  Items (target row y, channel octet cg, column quad xq) = 16 x 32 x 4, four per thread, xq and the low
+// four bits of cg over a wave's lanes: a load instruction reads the 64-B row pieces of 16 channels (the other
+// half of each 128-B line is the neighbouring column block's, whose workgroup xcd_block puts on the same XCD),
+// and an item's four 16-B LDS writes fall into all sixteen 16-B slots ((row + cg) mod 16 over a lane group).
+// Values as prep_pair + the bf16 staging give them: bf16(x * scale), channels >= C bf16(0 * scale), targets
+// off the map +0.
+struct StageItem {
+    int xq, cg, y;    // column quad, channel octet, (virtual) block row
+    int ty, tx;       // the quad's first target pixel
+};
+
+__device__ __forceinline__ StageItem stage_item(int id, int ty0, int tx0, bool paired) {
+    StageItem t;
+    t.xq = id & 3, t.cg = (id >> 2) & 31, t.y = id >> 7;
+    // virtual row y >= 8 of a paired block = row y - 8 of the next column block
+    const bool second = paired && t.y >= 8;
+    t.ty = ty0 + t.y - (second ? 8 : 0), t.tx = tx0 + 4 * t.xq + (second ? 16 : 0);
+    return t;
+}
+
+// pixel i of the item's quad: its 8 channels -> one 16-B channel octet of the LDS image
+__device__ __forceinline__ void stage_write_px(unsigned char* smem, const StageItem& t, int i, const float (&p)[8], int C,
+                                               int H, int W, float scale) {
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (__bf16)(t.ty < H && t.tx + i < W ? (t.cg * 8 + e < C ? p[e] : 0.0f) * scale : 0.0f);
+    *reinterpret_cast<bf16x8*>(smem + (size_t)pad_row(t.y, 4 * t.xq + i) * kPadRow + t.cg * 16) = o;
+}
+
+__device__ __forceinline__ void stage_a_f32(unsigned char* smem, const float* __restrict__ f2, int C, int H, int W,
+                                            float scale, int ty0, int tx0, bool paired, int tid) {
+    constexpr int kItems = 4;
+    const int N = H * W;
+    // a quad starts at a multiple of 4 columns, so float4 loads need W % 4 == 0 (then N % 4 == 0) and an aligned base;
+    // N < 2^22 keeps a 256-channel image's byte offsets in 32 bits
+    if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(f2) & 15) == 0 && N < (1 << 22)) {
+        // One item's 8 float4 in flight per thread (64 KiB per workgroup: the start-up is all workgroups reading
+        // at once, bound by bandwidth and not by the depth of one thread's queue), in a rolled loop.  The
+        // compiler schedules the tile loop's epilogue by the register pressure it has met in the function so
+        // far: with two items in flight (86 VGPRs here against the bf16 staging's 70) that schedule changes, and
+        // with four it interleaves the loads and the writes by itself.  No load is predicated: a quad off the
+        // map or a channel >= C reads a clamped one that stage_write_px drops, so the loads are one straight
+        // block of uniform base + 32-bit lane offset.
+#pragma unroll 1
+        for (int it = 0; it < kItems; ++it) {
+            const StageItem t = stage_item(it * 512 + tid, ty0, tx0, paired);
+            const unsigned pix = (unsigned)(min(t.ty, H - 1) * W + min(t.tx, W - 4));
+            float4 x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned c = (unsigned)min(t.cg * 8 + e, C - 1);
+                x[e] = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(f2) +
+                                                        (size_t)((c * (unsigned)N + pix) * 4u));
+            }
+            stage_write_px(smem, t, 0, {x[0].x, x[1].x, x[2].x, x[3].x, x[4].x, x[5].x, x[6].x, x[7].x}, C, H, W, scale);
+            stage_write_px(smem, t, 1, {x[0].y, x[1].y, x[2].y, x[3].y, x[4].y, x[5].y, x[6].y, x[7].y}, C, H, W, scale);
+            stage_write_px(smem, t, 2, {x[0].z, x[1].z, x[2].z, x[3].z, x[4].z, x[5].z, x[6].z, x[7].z}, C, H, W, scale);
+            stage_write_px(smem, t, 3, {x[0].w, x[1].w, x[2].w, x[3].w, x[4].w, x[5].w, x[6].w, x[7].w}, C, H, W, scale);
+        }
+        return;
+    }
+    // otherwise scalar loads, clamped as prep_pair clamps its partial quads, one pixel's 8 channels at a time
+#pragma unroll 1
+    for (int k = 0; k < 4 * kItems; ++k) {
+        const StageItem t = stage_item((k >> 2) * 512 + tid, ty0, tx0, paired);
+        const int i = k & 3;
+        const float* px = f2 + (size_t)min(t.ty, H - 1) * W + min(t.tx + i, W - 1);
+        float p[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) p[e] = px[(size_t)min(t.cg * 8 + e, C - 1) * N];
+        stage_write_px(smem, t, i, p, C, H, W, scale);
+    }
+}
+
 // Paired last block row (host: w8_balance): the last block row has at most 8 valid target rows and
 // W % 32 == 0, so two horizontally adjacent last-row blocks share one workgroup: rows 0-7 of its virtual
 // 16x16 block are block cb's rows, rows 8-15 block cb+1's (A staging and the stores' second-half delta
@@ -305,9 +396,14 @@ struct Bal {
 // owns the matrix pipe (free-running partners drift into lock step: PMC of the free-running kernel
 // showed VALU co-issued with MFMA in a third of its VALU cycles; 0.221 vs 0.242 ms,
 // profiles/gemm_ab_r02_pp.json).
-__global__ void __launch_bounds__(512, 1)
-corr_pyramid_w8(const __bf16* __restrict__ opA, const __bf16* __restrict__ opB, PyrGeom g, int qsplit,
-                __half* __restrict__ pyr, Bal bal) {
+//
+// A staging, two modes sharing everything else (kF32 is compile time: no branch reaches the tile loop):
+//  * bf16 (corr_pyramid_w8, after prep_pair): the block's rows of opA = bf16(fmap2 * scale), copied;
+//  * fp32 (corr_pyramid_w8_f32, after prep_queries): the LDS image built from fmap2 itself (stage_a_f32), bit
+//    for bit the same image, so opA's 2 x 28.8 MB round trip (cfg2) and half of the prep pass go away.
+template <bool kF32>
+__device__ __forceinline__ void w8_body(const void* srcA, int C, float scale, const __bf16* opB, const PyrGeom& g,
+                                        int qsplit, __half* pyr, const Bal& bal) {
     constexpr int Cp = 256, CPR = Cp / 8, WAVES = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -331,26 +427,30 @@ corr_pyramid_w8(const __bf16* __restrict__ opA, const __bf16* __restrict__ opB, 
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
 
-    const __bf16* gA = opA + (size_t)b * N * Cp;
-    // 16 pieces per thread, all loads in flight before the first LDS store (a load-store loop pays one
-    // HBM round trip per piece before the first MFMA)
-    constexpr int kPieces = 256 * CPR / (64 * WAVES);
-    uint4 av[kPieces];
+    if constexpr (kF32) {
+        stage_a_f32(smem, static_cast<const float*>(srcA) + (size_t)b * C * N, C, H, W, scale, ty0, tx0, paired, tid);
+    } else {
+        const __bf16* gA = static_cast<const __bf16*>(srcA) + (size_t)b * N * Cp;
+        // 16 pieces per thread, all loads in flight before the first LDS store (a load-store loop pays one
+        // HBM round trip per piece before the first MFMA)
+        constexpr int kPieces = 256 * CPR / (64 * WAVES);
+        uint4 av[kPieces];
 #pragma unroll
-    for (int i = 0; i < kPieces; ++i) {
-        const int id = tid + i * 64 * WAVES;
-        const int row = id / CPR, c = id - row * CPR;
-        // virtual row y >= 8 of a paired block = row y - 8 of the next column block
-        const bool second = paired && (row >> 4) >= 8;
-        const int ty = ty0 + (row >> 4) - (second ? 8 : 0), tx = tx0 + (row & 15) + (second ? 16 : 0);
-        av[i] = make_uint4(0, 0, 0, 0);
-        if (ty < H && tx < W) av[i] = *reinterpret_cast<const uint4*>(gA + (size_t)(ty * W + tx) * Cp + c * 8);
-    }
+        for (int i = 0; i < kPieces; ++i) {
+            const int id = tid + i * 64 * WAVES;
+            const int row = id / CPR, c = id - row * CPR;
+            // virtual row y >= 8 of a paired block = row y - 8 of the next column block
+            const bool second = paired && (row >> 4) >= 8;
+            const int ty = ty0 + (row >> 4) - (second ? 8 : 0), tx = tx0 + (row & 15) + (second ? 16 : 0);
+            av[i] = make_uint4(0, 0, 0, 0);
+            if (ty < H && tx < W) av[i] = *reinterpret_cast<const uint4*>(gA + (size_t)(ty * W + tx) * Cp + c * 8);
+        }
 #pragma unroll
-    for (int i = 0; i < kPieces; ++i) {
-        const int id = tid + i * 64 * WAVES;
-        const int row = id / CPR, c = id - row * CPR;
-        *reinterpret_cast<uint4*>(smem + (size_t)pad_row(row >> 4, row & 15) * kPadRow + c * 16) = av[i];
+        for (int i = 0; i < kPieces; ++i) {
+            const int id = tid + i * 64 * WAVES;
+            const int row = id / CPR, c = id - row * CPR;
+            *reinterpret_cast<uint4*>(smem + (size_t)pad_row(row >> 4, row & 15) * kPadRow + c * 16) = av[i];
+        }
     }
     __syncthreads();
 
@@ -426,6 +526,18 @@ corr_pyramid_w8(const __bf16* __restrict__ opA, const __bf16* __restrict__ opB, 
     if (!late) __builtin_amdgcn_s_barrier();
 }
 
+__global__ void __launch_bounds__(512, 1)
+corr_pyramid_w8(const __bf16* __restrict__ opA, const __bf16* __restrict__ opB, PyrGeom g, int qsplit,
+                __half* __restrict__ pyr, Bal bal) {
+    w8_body<false>(opA, 0, 0.0f, opB, g, qsplit, pyr, bal);
+}
+
+__global__ void __launch_bounds__(512, 1)
+corr_pyramid_w8_f32(const float* __restrict__ f2, const __bf16* __restrict__ opB, PyrGeom g, int qsplit,
+                    __half* __restrict__ pyr, Bal bal, int C, float scale) {
+    w8_body<true>(f2, C, scale, opB, g, qsplit, pyr, bal);
+}
+
 // query slots of the tiles layout for an H x W map (rmd.h)
 long long tiles_slots(int H, int W) {
     return (long long)(H / 2) * ((W + 15) / 16) * 32 + ((H & 1) ? (long long)(W + 31) / 32 * 32 : 0);
@@ -472,7 +584,23 @@ int prepare(const float* fmap1, const float* fmap2, int channels, float scale, c
     return check_launch("rmd_corr_prepare");
 }
 
-int pyramid(const rmd_pyramid_desc& d, void* pyramid, void* workspace, hipStream_t st) {
+// the B operand alone, at the offset prepare() puts it: what pyramid_staged() reads from the workspace
+int prepare_queries(const float* fmap1, int channels, const rmd_pyramid_desc& d, void* workspace, hipStream_t st) {
+    const int N = d.height * d.width;
+    __bf16* opB = reinterpret_cast<__bf16*>(workspace) + (size_t)d.batch * N * 256;
+    const int S = d.query_slots;
+    const int lds = kPrepPx * kPrepStride;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(prep_queries), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    prep_queries<<<dim3((S + kPrepPx - 1) / kPrepPx, d.batch), 512, lds, st>>>(fmap1, opB, channels, d.height, d.width, S,
+                                                                                S / 32);
+    return check_launch("rmd_corr_prepare_queries");
+}
+
+namespace {
+
+// fmap2 == nullptr: A from the workspace (prepare()); otherwise staged from fmap2 (prepare_queries())
+int launch_gemm(const float* fmap2, int channels, float scale, const rmd_pyramid_desc& d, void* pyramid, void* workspace,
+                hipStream_t st) {
     const int N = d.height * d.width;
     __bf16* opA = reinterpret_cast<__bf16*>(workspace);
     __bf16* opB = opA + (size_t)d.batch * N * 256;
@@ -483,9 +611,27 @@ int pyramid(const rmd_pyramid_desc& d, void* pyramid, void* workspace, hipStream
     while (nblk * d.batch * qs < 256 && qs * 32 <= nqt) qs *= 2;
     const int lds = 256 * (int)kPadRow;
     const Bal bal = w8_balance(d, qs);
+    if (fmap2) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(corr_pyramid_w8_f32),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        corr_pyramid_w8_f32<<<bal.nwg, 512, lds, st>>>(fmap2, opB, make_geom(d), qs, reinterpret_cast<__half*>(pyramid), bal,
+                                                       channels, scale);
+        return check_launch("rmd_corr_pyramid/gemm-w8-f32");
+    }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(corr_pyramid_w8), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     corr_pyramid_w8<<<bal.nwg, 512, lds, st>>>(opA, opB, make_geom(d), qs, reinterpret_cast<__half*>(pyramid), bal);
     return check_launch("rmd_corr_pyramid/gemm-w8");
+}
+
+}  // namespace
+
+int pyramid(const rmd_pyramid_desc& d, void* pyramid, void* workspace, hipStream_t st) {
+    return launch_gemm(nullptr, 0, 0.0f, d, pyramid, workspace, st);
+}
+
+int pyramid_staged(const float* fmap2, int channels, float scale, const rmd_pyramid_desc& d, void* pyramid,
+                   void* workspace, hipStream_t st) {
+    return launch_gemm(fmap2, channels, scale, d, pyramid, workspace, st);
 }
 
 }  // namespace w8

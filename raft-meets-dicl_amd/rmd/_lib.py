@@ -72,6 +72,9 @@ _SIGS = {
     "rmd_corr_gemm_kernel": (ctypes.c_char_p, [ctypes.POINTER(PyramidDesc), _I, _I]),
     "rmd_corr_prepare": (_I, [_P, _P, _I, ctypes.c_float, ctypes.POINTER(PyramidDesc), _I, _P, _P]),
     "rmd_corr_pyramid_prepared": (_I, [_I, ctypes.c_float, ctypes.POINTER(PyramidDesc), _I, _P, _P, _P]),
+    "rmd_corr_pyramid_fused": (_I, [_P, _P, _I, ctypes.c_float, ctypes.POINTER(PyramidDesc), _I, _P, _P, _P]),
+    "rmd_corr_prepare_queries": (_I, [_P, _I, ctypes.POINTER(PyramidDesc), _I, _P, _P]),
+    "rmd_corr_pyramid_staged": (_I, [_P, _I, ctypes.c_float, ctypes.POINTER(PyramidDesc), _I, _P, _P, _P]),
     "rmd_corr_otf_workspace_bytes": (ctypes.c_size_t, [_I] * 6),
     "rmd_corr_otf_prepare": (_I, [_P, _P] + [_I] * 5 + [ctypes.c_float, _I, _P, _P]),
     "rmd_corr_otf_lookup": (_I, [_P] + [_I] * 6 + [_P, _I, _U, _P, _P]),

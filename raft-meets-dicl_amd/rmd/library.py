@@ -324,7 +324,7 @@ def _corr_pyramid(fmap1, fmap2, levels, compute, storage, scale):
     _check_fmaps(fmap1, fmap2)
     f1, f2 = _f32(fmap1), _f32(fmap2)
     d, data, ws = pyramid_buffers(f1, levels, compute, storage)
-    _lib.launch("rmd_corr_pyramid", f1, f1, f2, f1.shape[1], float(scale), ctypes.byref(d), compute, data, ws)
+    _lib.launch("rmd_corr_pyramid_fused", f1, f1, f2, f1.shape[1], float(scale), ctypes.byref(d), compute, data, ws)
     return data
 
 

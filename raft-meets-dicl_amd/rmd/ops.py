@@ -105,7 +105,9 @@ def corr_pyramid(fmap1, fmap2, levels=4, precision=None, events=None, scale=None
 
     ``events`` (optional list) receives (start, end) HIP events bracketing the GEMM launch alone
     (the operand prep runs before the start event) — bench.py's roofline timing; that call runs the
-    same two C-ABI halves (rmd_corr_prepare, rmd_corr_pyramid_prepared) directly.
+    two C-ABI halves of what the operator runs directly: rmd_corr_prepare_queries + rmd_corr_pyramid_staged
+    on the w8 GEMM (whose launch then includes staging fmap2 from fp32), rmd_corr_prepare +
+    rmd_corr_pyramid_prepared on every other.
     """
     _same_device(fmap1, fmap2)
     if fmap1.shape != fmap2.shape or fmap1.dim() != 4:
@@ -121,11 +123,18 @@ def corr_pyramid(fmap1, fmap2, levels=4, precision=None, events=None, scale=None
     _require_gpu(fmap1, fmap2)
     f1, f2 = _f32(fmap1), _f32(fmap2)
     d, data, ws = library.pyramid_buffers(f1, levels, compute, storage)
+    staged = _lib.lib().rmd_corr_gemm_kernel(ctypes.byref(d), c, compute) == b"w8"
     with torch.cuda.device(f1.device):                  # the events record on this device's current stream
-        _lib.launch("rmd_corr_prepare", f1, f1, f2, c, scale, ctypes.byref(d), compute, ws)
+        if staged:
+            _lib.launch("rmd_corr_prepare_queries", f1, f1, c, ctypes.byref(d), compute, ws)
+        else:
+            _lib.launch("rmd_corr_prepare", f1, f1, f2, c, scale, ctypes.byref(d), compute, ws)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.launch("rmd_corr_pyramid_prepared", f1, c, scale, ctypes.byref(d), compute, data, ws)
+        if staged:
+            _lib.launch("rmd_corr_pyramid_staged", f1, f2, c, scale, ctypes.byref(d), compute, data, ws)
+        else:
+            _lib.launch("rmd_corr_pyramid_prepared", f1, c, scale, ctypes.byref(d), compute, data, ws)
         e1.record()
         events.append((e0, e1))
     return Pyramid(data, d, c, scale)
