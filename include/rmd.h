@@ -783,6 +783,45 @@ int rmd_motion_encoder(const float* flow, const float* corr, const float* const*
                        void* stream);
 
 /*
+ * The backward of rmd_conv2d in the parity mode (RMD_BF16X3), for training the same convolutions
+ * (BasicMotionEncoder raft.py:193-225, FlowHead raft.py:262-273, Up8Network's mask head raft.py:299-331) under
+ * autograd.  With x = cat(in0, in1), y = act(conv(x, W) + b), grad = dL/dy (B, Cout, H, W) and gm = grad where
+ * !(y <= 0) and exactly 0 elsewhere (act = 1; a NaN in y keeps the gradient, as torch.relu's backward) or
+ * gm = grad (act = 0, y = NULL):
+ *   grad_bias[o]           = sum_{b,y,x} gm[b, o, y, x]                          (float64 sums, fixed order)
+ *   grad_in[b, c, y, x]    = sum_{o,i,j} W[o, c, i, j] gm[b, o, y - i + kh/2, x - j + kw/2]
+ *   grad_weight[o,c,i,j]   = sum_{b,y,x} gm[b, o, y, x] x[b, c, y + i - kh/2, x + j - kw/2]   (zero outside the map)
+ * grad_in0 (B, C0, H, W) and grad_in1 (B, C1, H, W) are the two channel ranges of grad_in, written to two tensors.
+ * Any of the four outputs may be NULL: that gradient is not computed and its kernels are not launched.  y is
+ * NULL exactly when act = 0, in1 exactly when C1 = 0 (grad_in1 must then be NULL).  The data gradient is
+ * rmd_conv2d's own kernel over gm behind the flipped, transposed weights (its contraction runs over Cout, up to
+ * 1024); the weight gradient is an MFMA GEMM with the pixels on K whose per-slice partials are summed in a fixed
+ * order.  Three split-bf16 products, fp32 accumulators, no atomics: bitwise reproducible, and grad_in of one sample
+ * does not depend on the others.  A NaN in gm reaches exactly the grad_in positions whose transposed receptive
+ * field holds it, and every element of grad_weight[o] and grad_bias[o] of its channel o.
+ * Supported (rmd_conv2d_backward_supported, host only): the shapes of rmd_conv2d, with (C0 + C1) H W < 2^30 and
+ * Cout H W < 2^30.  No output may overlap an input, another output or the workspace (RMD_ERR_ARG).  `workspace`
+ * holds rmd_conv2d_backward_workspace_bytes() bytes (0 = unsupported arguments), whichever outputs are asked for
+ *   = gm        align256(4 B Cout H W)
+ *   + packed W' for each source of n = C0, C1 > 0 channels: ceil(n / 32) 32 x kh kw x ceil(Cout / 16) 16 elements
+ *               x 2 parts x 2 bytes, + align256(4 x 32 ceil(n / 32)) bytes of the zero bias the forward kernel adds
+ *   + partials  align256(4 S Cout (C0 + C1) kh kw), S = max(1, min(B H, 32, ceil(1024 / (ceil(Cout / 128)
+ *               ceil((C0 + C1) / 32) kh)))) slices of the (image, row) list
+ *   + 256
+ * and may be reused by the next call on the same stream.  The launcher never allocates, frees or synchronises,
+ * reads no environment variable, and all argument checks run before any launch.
+ */
+int rmd_conv2d_backward_supported(int kh, int kw, int c0, int c1, int cout);
+/* The kernels a call with these outputs (non-zero: wanted) launches, in order, separated by spaces: "mask_bias"
+ * ("mask_bias+gm" where it writes gm), "pack0 conv0", "pack1 conv1", "wgrad reduce"; "" for no output.  Host only. */
+const char* rmd_conv2d_backward_kernels(int want_in0, int want_in1, int want_weight, int want_bias, int act);
+size_t rmd_conv2d_backward_workspace_bytes(int batch, int c0, int c1, int cout, int kh, int kw, int height, int width);
+int rmd_conv2d_backward(const float* grad, const float* y /* NULL iff act == 0 */, const float* in0, const float* in1,
+                        const float* weight, float* grad_in0, float* grad_in1, float* grad_weight, float* grad_bias,
+                        void* workspace, int batch, int c0, int c1, int cout, int kh, int kw, int height, int width,
+                        int act, void* stream);
+
+/*
  * RAFT's feature / context encoder, inference only: FeatureEncoder (common/encoders/raft/s3.py:8-72) and its
  * ResidualBlock (common/blocks/raft.py:13-46) for the norm types 'none' and 'instance' (eval-mode batch norm
  * arrives folded into the weights and biases: norm none).  All maps float32 NCHW.

@@ -31,6 +31,7 @@
 // and does not depend on the batch, on the other tiles or on the slice offset: results are bitwise repeatable
 // and per-sample independent.
 
+#include "conv_internal.h"
 #include "mfma_bf16.h"
 
 namespace rmd {
@@ -331,6 +332,19 @@ EncWork enc_carve(char* base, int batch, int corr_planes, int height, int width)
 }
 
 }  // namespace
+
+// ---- the door of conv_backward.hip (conv_internal.h) -------------------------------------------------
+
+size_t conv_fragment_bytes(int c, int cout, int kh, int kw) { return conv_packed_bytes(c, cout, kh, kw); }
+
+void conv_run_prepacked(const float* in, const void* frags, const float* bias, float* out, int batch, int c, int cout,
+                        int kh, int kw, int height, int width, hipStream_t st) {
+    const ConvGeom P = conv_geom(batch, c, 0, cout, kh, kw, height, width, cout, 0, 0);
+    const bf16x8* fr = reinterpret_cast<const bf16x8*>(frags);
+    if (P.kc == 64) conv_launch<3, 64>(in, nullptr, fr, bias, out, P, st);
+    else conv_launch<3, 32>(in, nullptr, fr, bias, out, P, st);
+}
+
 }  // namespace rmd
 
 using namespace rmd;

@@ -132,6 +132,10 @@ _SIGS = {
     "rmd_conv2d_supported": (_I, [_I] * 5),
     "rmd_conv2d_workspace_bytes": (ctypes.c_size_t, [_I] * 5),
     "rmd_conv2d": (_I, [_P] * 6 + [_I] * 12 + [_P]),
+    "rmd_conv2d_backward_supported": (_I, [_I] * 5),
+    "rmd_conv2d_backward_kernels": (ctypes.c_char_p, [_I] * 5),
+    "rmd_conv2d_backward_workspace_bytes": (ctypes.c_size_t, [_I] * 8),
+    "rmd_conv2d_backward": (_I, [_P] * 10 + [_I] * 9 + [_P]),
     "rmd_motion_encoder_workspace_bytes": (ctypes.c_size_t, [_I] * 4),
     "rmd_motion_encoder": (_I, [_P] * 6 + [_I] * 5 + [_P]),
     "rmd_conv2d_strided_supported": (_I, [_I] * 5),

@@ -23,7 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .library import (INSTANCE_NORM_EPS, LIB, _OPS, _STORAGE, check_attn_args, check_conv_args, check_encoder_args,
+from .library import (INSTANCE_NORM_EPS, LIB, _OPS, _STORAGE, check_attn_args, check_conv_args, check_conv_backward_args,
+                      check_encoder_args,
                       check_feature_encoder_args, check_gru_args, check_join_args, check_mnet_args,
                       check_norm_conv_args, check_stats_args, check_tail_args,
                       check_head_args, check_loss_args, check_match_args, check_match_backward_args, check_metric_args,
@@ -611,6 +612,31 @@ def conv2d_act(x0, x1, weight, bias, act, compute):
     x = x0.detach().float() if x1 is None else torch.cat([x0.detach().float(), x1.detach().float()], dim=1)
     out = F.conv2d(x, weight.detach().float(), bias.detach().float().reshape(-1), padding=(kh // 2, kw // 2))
     return F.relu(out) if act else out
+
+
+def conv2d_act_train(x0, x1, weight, bias, act):
+    """The same composite with its ATen graph recorded (AutogradCPU)."""
+    _, _, _, kh, kw = check_conv_args(x0, x1, weight, bias, act, _lib.RMD_BF16X3)
+    x = x0.float() if x1 is None else torch.cat([x0.float(), x1.float()], dim=1)
+    out = F.conv2d(x, weight.float(), bias.float().reshape(-1), padding=(kh // 2, kw // 2))
+    return F.relu(out) if act else out
+
+
+def conv2d_act_backward(grad, y, x0, x1, weight, act, needs_grad):
+    """torch.autograd.grad of conv2d_act_train's composite, its ReLU masked by the y given; (0,) tensors for a
+    skipped gradient."""
+    _, _, cout, kh, kw = check_conv_backward_args(grad, y, x0, x1, weight, act, needs_grad)
+    needs = [needs_grad[0], needs_grad[1] and x1 is not None, needs_grad[2], needs_grad[3]]
+    g = grad.detach().float()
+    if act:
+        g = torch.where(y.detach() <= 0, torch.zeros_like(g), g)        # !(y <= 0) keeps the gradient: NaN too
+    with torch.enable_grad():
+        ins = [None if t is None else t.detach().float().requires_grad_(True)
+               for t in (x0, x1, weight, weight.new_zeros(cout))]
+        out = conv2d_act_train(ins[0], ins[1], ins[2], ins[3], 0)
+        wanted = [t for t, need in zip(ins, needs) if need]
+        got = iter(torch.autograd.grad(out, wanted, g) if wanted else ())
+    return [next(got) if need else x0.new_empty((0,), dtype=torch.float32) for need in needs]
 
 
 def motion_encoder(flow, corr, weights, biases, compute):

@@ -9,8 +9,8 @@
 
 The convolutions of Up8Network are MIOpen's by default (`conv1`, `relu1`, `conv2`: state_dict keys and forward
 hooks unchanged) and, with fused="auto" / "on" in inference, two torch.ops.rmd.conv2d_act (csrc/conv.hip; the
-modes are those of rmd.update, and hooks on the inner modules then do not fire); the softmax + 3x3 convex
-combination runs as rmd_up8.  Soft-argmax runs as one rmd_softargmax launch over all levels; the DAP variants
+modes are those of rmd.update, fused_backward for training included, and hooks on the inner modules then do not
+fire); the softmax + 3x3 convex combination runs as rmd_up8.  Soft-argmax runs as one rmd_softargmax launch over all levels; the DAP variants
 call their `dap` modules (rmd_dap) first.  Both are autograd functions with HIP backward kernels.
 """
 
@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .update import check_fused_arguments, conv_fallback_reason
+from .update import check_fused_arguments, conv_fallback_reason, conv_needs_grad
 from .blocks.dicl import DisplacementAwareProjection
 
 
@@ -31,11 +31,12 @@ class Up8Network(nn.Module):
     """RAFT 8x flow upsampling module for the finest level (raft.py:299-331)."""
 
     def __init__(self, hidden_dim=128, mixed_precision=False, relu_inplace=True, temperature=4.0, fused="off",
-                 precision="fp32"):
+                 precision="fp32", fused_backward=False):
         super().__init__()
         check_fused_arguments("Up8Network", fused, precision)
         self.fused = fused
         self.precision = precision
+        self.fused_backward = bool(fused_backward)
         self.mixed_precision = mixed_precision
         self.conv1 = nn.Conv2d(hidden_dim, 256, 3, padding=1)
         self.relu1 = nn.ReLU(inplace=relu_inplace)
@@ -46,14 +47,15 @@ class Up8Network(nn.Module):
         """Why the fused mask head cannot serve this call (None if it can)."""
         if self.mixed_precision:
             return "mixed_precision=True (the mask head then runs under autocast)"
-        return conv_fallback_reason([hidden], (self.conv1, self.conv2))
+        return conv_fallback_reason([hidden], (self.conv1, self.conv2), self.fused_backward, self.precision)
 
     def forward(self, hidden, flow):
         if self.fused != "off":
             reason = self.fallback_reason(hidden)
             if reason is None:
-                mask = ops.conv2d_act(hidden, None, self.conv1.weight, self.conv1.bias, "relu", self.precision)
-                mask = ops.conv2d_act(mask, None, self.conv2.weight, self.conv2.bias, "none", self.precision)
+                train = conv_needs_grad([hidden], (self.conv1, self.conv2))
+                mask = ops.conv2d_act(hidden, None, self.conv1.weight, self.conv1.bias, "relu", self.precision, train)
+                mask = ops.conv2d_act(mask, None, self.conv2.weight, self.conv2.bias, "none", self.precision, train)
                 return ops.up8(mask, flow, self.temperature)
             if self.fused == "on":
                 raise RuntimeError(f"Up8Network(fused='on'): {reason}")

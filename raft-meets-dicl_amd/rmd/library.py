@@ -30,6 +30,7 @@ follow SURVEY.md §8(b):
         / dicl_match_1x1_backward(grad, ..., needs_grad) -> grads[]          its formula recomputes from the inputs
   sepconv_gru(h, x, weights[], biases[], compute) -> (B, Hd, H, W)           raft.py:228-259 (inference)
   conv2d_act(x0, x1?, weight, bias, act, compute) -> (B, Cout, H, W)         raft.py:193-225, 262-273, 299-331
+  conv2d_act_train(x0, x1?, weight, bias, act) / conv2d_act_backward(...)    the same, differentiable (fp32 mode)
   motion_encoder(flow, corr, weights[], biases[], compute) -> (B, 128, H, W) raft.py:193-225 (both inference)
   conv2d_norm_act / instance_norm_stats / residual_join / feature_encoder     encoders/raft/s3.py:8-72,
                                                                               blocks/raft.py:13-46 (inference)
@@ -52,9 +53,10 @@ from . import _lib
 LIB = torch.library.Library("rmd", "DEF")
 
 # name -> (family, schema without the name).  Families: "model" is the SURVEY.md §8(b) model-operator
-# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update", "conv", "encoder" and "mnet"
-# are listed by loss_operators(), metric_operators(), head_operators(), attn_operators(), match_operators(),
-# match_train_operators(), update_operators(), conv_operators(), encoder_operators() and mnet_operators().
+# set (operators()); "loss", "metric", "head", "attn", "match", "match_train", "update", "conv", "conv_train",
+# "encoder" and "mnet" are listed by loss_operators(), metric_operators(), head_operators(), attn_operators(),
+# match_operators(), match_train_operators(), update_operators(), conv_operators(), conv_train_operators(),
+# encoder_operators() and mnet_operators().
 _OPS = {
     "corr_pyramid": ("model", "(Tensor fmap1, Tensor fmap2, int levels, int compute, int storage, float scale) "
                               "-> Tensor"),
@@ -102,6 +104,9 @@ _OPS = {
     "sepconv_gru": ("update", "(Tensor h, Tensor x, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
     "conv2d_act": ("conv", "(Tensor x0, Tensor? x1, Tensor weight, Tensor bias, int act, int compute) -> Tensor"),
     "motion_encoder": ("conv", "(Tensor flow, Tensor corr, Tensor[] weights, Tensor[] biases, int compute) -> Tensor"),
+    "conv2d_act_train": ("conv_train", "(Tensor x0, Tensor? x1, Tensor weight, Tensor bias, int act) -> Tensor"),
+    "conv2d_act_backward": ("conv_train", "(Tensor grad, Tensor? y, Tensor x0, Tensor? x1, Tensor weight, int act, "
+                                          "bool[] needs_grad) -> Tensor[]"),
     "conv2d_norm_act": ("encoder", "(Tensor x, Tensor? scale, Tensor? shift, Tensor weight, Tensor bias, "
                                    "Tensor? residual, int stride, int act, int compute) -> Tensor"),
     "instance_norm_stats": ("encoder", "(Tensor x, float eps) -> (Tensor, Tensor)"),
@@ -163,6 +168,11 @@ def update_operators():
 def conv_operators():
     """Names of the registered torch.ops.rmd update-block convolution operators."""
     return _family("conv")
+
+
+def conv_train_operators():
+    """Names of the registered torch.ops.rmd differentiable update-block convolution operators."""
+    return _family("conv_train")
 
 
 def encoder_operators():
@@ -1533,6 +1543,105 @@ def _motion_encoder_below_autograd(flow, corr, weights, biases, compute):
 
 LIB.impl("conv2d_act", _conv2d_act_below_autograd, "Autograd")
 LIB.impl("motion_encoder", _motion_encoder_below_autograd, "Autograd")
+
+
+# ---- fused k x k convolutions, training (csrc/conv_backward.hip) ------------------------------------
+#
+# conv2d_act_train: conv2d_act's kernel in the parity mode (bit for bit its result) with an autograd formula that
+# saves x0, x1, weight and the output.  conv2d_act_backward(grad, y, x0, x1, weight, act, needs_grad) returns
+# [gx0, gx1, gweight, gbias], an empty tensor for what needs_grad = [x0, x1, weight, bias] switches off (and for
+# gx1 without an x1); y is the forward's output, given exactly when act is 1.  The one-product mode has no backward.
+
+def check_conv_backward_args(grad, y, x0, x1, weight, act, needs_grad):
+    """check_conv_args plus the shapes of grad and y and the four needs_grad flags; returns (C0, C1, Cout, kh, kw)."""
+    name = "conv2d_act_backward"
+    if weight.dim() != 4:
+        raise ValueError(f"{name}: weight must be 4-D, got {tuple(weight.shape)}")
+    dims = check_conv_args(x0, x1, weight, weight.new_empty(weight.shape[0]), act, _lib.RMD_BF16X3)
+    want = (x0.shape[0], dims[2], x0.shape[2], x0.shape[3])
+    if tuple(grad.shape) != want or not grad.is_floating_point():
+        raise ValueError(f"{name}: grad must be a floating-point {want} tensor, got {grad.dtype} {tuple(grad.shape)}")
+    if (y is None) != (act == 0):
+        raise ValueError(f"{name}: y (the forward's output) must be given exactly when act is 1 (ReLU)")
+    if y is not None and (tuple(y.shape) != want or not y.is_floating_point()):
+        raise ValueError(f"{name}: y must be a floating-point {want} tensor, got {y.dtype} {tuple(y.shape)}")
+    if len(needs_grad) != 4:
+        raise ValueError(f"{name}: needs_grad is [x0, x1, weight, bias], got {len(needs_grad)} flags")
+    return dims
+
+
+def conv_backward_supported(kh, kw, c0, c1, cout):
+    """rmd_conv2d_backward_supported: whether the HIP backward serves this convolution (host only)."""
+    return bool(_lib.lib().rmd_conv2d_backward_supported(kh, kw, c0, c1, cout))
+
+
+def conv_backward_kernels(needs_grad, act, has_x1=True):
+    """rmd_conv2d_backward_kernels: the names of the kernels conv2d_act_backward launches for these needs_grad flags
+    [x0, x1, weight, bias], in order (host only)."""
+    n0, n1, nw, nb = (int(bool(v)) for v in needs_grad)
+    return _lib.lib().rmd_conv2d_backward_kernels(n0, n1 if has_x1 else 0, nw, nb, act).decode().split()
+
+
+def _conv_grads(x0, x1, weight, needs_grad):
+    """The four gradients, shaped like what they belong to; (0,) for a skipped one and for gx1 without an x1."""
+    shapes = [x0.shape, None if x1 is None else x1.shape, weight.shape, (weight.shape[0],)]
+    return [_like(x0, tuple(s) if need and s is not None else (0,)) for s, need in zip(shapes, needs_grad)]
+
+
+@_hip("conv2d_act_train")
+def _conv2d_act_train(x0, x1, weight, bias, act):
+    return _conv2d_act(x0, x1, weight, bias, act, _lib.RMD_BF16X3)
+
+
+@_fake("conv2d_act_train")
+def _(x0, x1, weight, bias, act):
+    _, _, cout, _, _ = check_conv_args(x0, x1, weight, bias, act, _lib.RMD_BF16X3)
+    return _like(x0, (x0.shape[0], cout, x0.shape[2], x0.shape[3]))
+
+
+@_hip("conv2d_act_backward")
+def _conv2d_act_backward(grad, y, x0, x1, weight, act, needs_grad):
+    c0, c1, cout, kh, kw = check_conv_backward_args(grad, y, x0, x1, weight, act, needs_grad)
+    b, _, ht, wd = x0.shape
+    reason = conv_unsupported_reason(kh, kw, c0, c1, cout, ht, wd)
+    if reason or not conv_backward_supported(kh, kw, c0, c1, cout):
+        raise ValueError(f"conv2d_act_backward: unsupported on the GPU: {reason or 'unsupported convolution'}")
+    g, yy = _f32(grad), (None if y is None else _f32(y))
+    a0, a1, wt = _f32(x0), (None if x1 is None else _f32(x1)), _f32(weight)
+    grads = _conv_grads(a0, a1, wt, needs_grad)
+    if any(t.numel() for t in grads):
+        work = _lib.workspace("conv2d_backward", a0, b, c0, c1, cout, kh, kw, ht, wd)
+        gx0, gx1, gw, gb = [t if t.numel() else None for t in grads]
+        _lib.launch("rmd_conv2d_backward", a0, g, yy, a0, a1, wt, gx0, gx1, gw, gb, work, b, c0, c1, cout, kh, kw, ht,
+                    wd, act)
+    return grads
+
+
+@_fake("conv2d_act_backward")
+def _(grad, y, x0, x1, weight, act, needs_grad):
+    check_conv_backward_args(grad, y, x0, x1, weight, act, needs_grad)
+    return _conv_grads(x0, x1, weight, needs_grad)
+
+
+def _conv_train_setup(ctx, inputs, output):
+    x0, x1, weight, bias, act = inputs
+    ctx.save_for_backward(x0, x1, weight, output if act else None)
+    ctx.act = act
+    ctx.bias_dtype = bias.dtype
+    ctx.needs = [x0.requires_grad, x1 is not None and x1.requires_grad, weight.requires_grad, bias.requires_grad]
+
+
+def _conv_train_bwd(ctx, grad):
+    x0, x1, weight, y = ctx.saved_tensors
+    if not any(ctx.needs):
+        return None, None, None, None, None
+    grads = torch.ops.rmd.conv2d_act_backward(grad, y, x0, x1, weight, ctx.act, ctx.needs)
+    dtypes = [x0.dtype, None if x1 is None else x1.dtype, weight.dtype, ctx.bias_dtype]
+    out = [g.to(d) if need else None for g, d, need in zip(grads, dtypes, ctx.needs)]
+    return out[0], out[1], out[2], out[3], None
+
+
+torch.library.register_autograd("rmd::conv2d_act_train", _conv_train_bwd, setup_context=_conv_train_setup)
 
 
 # ---- the feature / context encoder (encoders/raft/s3.py:8-72, blocks/raft.py:13-46), inference ------------

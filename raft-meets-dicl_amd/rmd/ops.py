@@ -510,16 +510,22 @@ CONV_PRECISIONS = MATCH_PRECISIONS
 CONV_ACTS = {"none": 0, "relu": 1}
 
 
-def conv2d_act(x0, x1, weight, bias, act="none", precision="fp32"):
-    """Fused convolution (torch.ops.rmd.conv2d_act; raft.py:193-225, 262-273, 299-331), inference only: a stride-1,
+def conv2d_act(x0, x1, weight, bias, act="none", precision="fp32", differentiable=False):
+    """Fused convolution (torch.ops.rmd.conv2d_act; raft.py:193-225, 262-273, 299-331): a stride-1,
     "same"-padded convolution over cat(x0 (B, C0, H, W), x1 (B, C1, H, W) or None) with weight (Cout, C0 + C1,
     kh, kw), kh and kw odd, bias (Cout,) and act "none" or "relu" -> (B, Cout, H, W).  precision "fp32": three
-    split-bf16 products (parity mode); "bf16": one.  Not differentiable."""
+    split-bf16 products (parity mode); "bf16": one.  Not differentiable unless differentiable=True, which routes to
+    torch.ops.rmd.conv2d_act_train: the same result bit for bit (fp32 only), whose backward (rmd_conv2d_backward)
+    reaches x0, x1, weight and bias."""
     if precision not in CONV_PRECISIONS:
         raise ValueError(f"conv2d_act: unknown precision '{precision}', expected one of {sorted(CONV_PRECISIONS)}")
     if act not in CONV_ACTS:
         raise ValueError(f"conv2d_act: unknown activation '{act}', expected one of {sorted(CONV_ACTS)}")
+    if differentiable and precision != "fp32":
+        raise ValueError("conv2d_act: the one-product mode has no backward (differentiable=True needs precision='fp32')")
     _same_device(x0, *([] if x1 is None else [x1]), weight, bias)
+    if differentiable:
+        return torch.ops.rmd.conv2d_act_train(x0, x1, weight, bias, CONV_ACTS[act])
     return torch.ops.rmd.conv2d_act(x0, x1, weight, bias, CONV_ACTS[act], CONV_PRECISIONS[precision])
 
 

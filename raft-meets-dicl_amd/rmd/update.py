@@ -13,6 +13,9 @@ convolutions with ReLU epilogues writing channel slices, no cat.  FlowHead: two 
           mode off, or neither h, x nor a parameter requires grad) and the widths are supported; the
           composition otherwise.  CPU tensors run the operator's CPU kernel under the same conditions.
   "on"    as "auto", but a RuntimeError naming the reason where "auto" would fall back.
+``fused_backward`` (BasicMotionEncoder, FlowHead, BasicUpdateBlock; default False): with "auto" / "on", a call that
+needs a gradient runs on torch.ops.rmd.conv2d_act_train (csrc/conv_backward.hip: data, weight and bias gradients
+in HIP) under the same conditions, in the fp32 mode only.  The recurrent unit keeps its eager training path.
 ``precision`` is the operator's: "fp32" (three split-bf16 products, the parity mode) or "bf16" (one).
 
 Forward hooks on the inner convolutions (and FlowHead's relu) do not fire on the fused paths (they are never
@@ -35,9 +38,16 @@ def check_fused_arguments(name, fused, precision):
         raise ValueError(f"{name}: unknown precision '{precision}', expected one of {sorted(ops.CONV_PRECISIONS)}")
 
 
-def conv_fallback_reason(inputs, convs):
+def conv_needs_grad(inputs, convs):
+    """Whether a call on `inputs` through the Conv2d modules `convs` records a graph."""
+    tensors = list(inputs) + [p for c in convs for p in (c.weight, c.bias)]
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def conv_fallback_reason(inputs, convs, fused_backward=False, precision="fp32"):
     """Why the fused convolution operators cannot serve `inputs` (4-D maps of one size) through the Conv2d modules
-    `convs` (None if they can): the conditions SepConvGru.fallback_reason documents."""
+    `convs` (None if they can): the conditions SepConvGru.fallback_reason documents.  With fused_backward a call
+    that needs a gradient is served too (torch.ops.rmd.conv2d_act_train), in the fp32 mode only."""
     tensors = list(inputs) + [p for c in convs for p in (c.weight, c.bias)]
     first = inputs[0]
     if any(t.device != first.device for t in tensors):
@@ -47,7 +57,10 @@ def conv_fallback_reason(inputs, convs):
     if torch.is_autocast_enabled() or (first.device.type == "cpu" and torch.is_autocast_enabled("cpu")):
         return "autocast is on"
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        return "a gradient is needed (the fused convolutions are inference only)"
+        if not fused_backward:
+            return "a gradient is needed (the fused convolutions are inference only)"
+        if precision != "fp32":
+            return "a gradient is needed and the fused backward is fp32 only (precision='bf16' has no backward)"
     if any(t.dim() != 4 for t in inputs):
         return f"the inputs must be 4-D, got {[tuple(t.shape) for t in inputs]}"
     if first.is_cuda:
@@ -63,11 +76,12 @@ def conv_fallback_reason(inputs, convs):
 class BasicMotionEncoder(nn.Module):
     """Encoder to combine correlation and flow for GRU input (raft.py:193-225)"""
 
-    def __init__(self, corr_planes, fused="off", precision="fp32"):
+    def __init__(self, corr_planes, fused="off", precision="fp32", fused_backward=False):
         super().__init__()
         check_fused_arguments("BasicMotionEncoder", fused, precision)
         self.fused = fused
         self.precision = precision
+        self.fused_backward = bool(fused_backward)
 
         self.convc1 = nn.Conv2d(corr_planes, 256, 1, padding=0)
         self.convc2 = nn.Conv2d(256, 192, 3, padding=1)
@@ -84,13 +98,23 @@ class BasicMotionEncoder(nn.Module):
 
     def fallback_reason(self, flow, corr):
         """Why the fused operator cannot serve this call (None if it can)."""
-        return conv_fallback_reason([flow, corr], self._convs())
+        return conv_fallback_reason([flow, corr], self._convs(), self.fused_backward, self.precision)
+
+    def _train(self, flow, corr):
+        """The five convolutions as differentiable operators; `conv` reads (cor, flo) as its two sources."""
+        def conv(x0, x1, m):
+            return ops.conv2d_act(x0, x1, m.weight, m.bias, "relu", "fp32", differentiable=True)
+        cor = conv(conv(corr, None, self.convc1), None, self.convc2)
+        flo = conv(conv(flow, None, self.convf1), None, self.convf2)
+        return torch.cat([conv(cor, flo, self.conv), flow], dim=1)
 
     def forward(self, flow, corr):
         if self.fused != "off":
             reason = self.fallback_reason(flow, corr)
             if reason is None:
                 convs = self._convs()
+                if conv_needs_grad([flow, corr], convs):
+                    return self._train(flow, corr)
                 return ops.motion_encoder(flow, corr, [c.weight for c in convs], [c.bias for c in convs],
                                           self.precision)
             if self.fused == "on":
@@ -185,11 +209,13 @@ class SepConvGru(nn.Module):
 class FlowHead(nn.Module):
     """Head to compute delta-flow from GRU hidden-state (raft.py:262-273)"""
 
-    def __init__(self, input_dim=128, hidden_dim=256, relu_inplace=True, fused="off", precision="fp32"):
+    def __init__(self, input_dim=128, hidden_dim=256, relu_inplace=True, fused="off", precision="fp32",
+                 fused_backward=False):
         super().__init__()
         check_fused_arguments("FlowHead", fused, precision)
         self.fused = fused
         self.precision = precision
+        self.fused_backward = bool(fused_backward)
 
         self.conv1 = nn.Conv2d(input_dim, hidden_dim, 3, padding=1)
         self.conv2 = nn.Conv2d(hidden_dim, 2, 3, padding=1)
@@ -197,14 +223,15 @@ class FlowHead(nn.Module):
 
     def fallback_reason(self, x):
         """Why the fused operator cannot serve this call (None if it can)."""
-        return conv_fallback_reason([x], (self.conv1, self.conv2))
+        return conv_fallback_reason([x], (self.conv1, self.conv2), self.fused_backward, self.precision)
 
     def forward(self, x):
         if self.fused != "off":
             reason = self.fallback_reason(x)
             if reason is None:
-                y = ops.conv2d_act(x, None, self.conv1.weight, self.conv1.bias, "relu", self.precision)
-                return ops.conv2d_act(y, None, self.conv2.weight, self.conv2.bias, "none", self.precision)
+                train = conv_needs_grad([x], (self.conv1, self.conv2))
+                y = ops.conv2d_act(x, None, self.conv1.weight, self.conv1.bias, "relu", self.precision, train)
+                return ops.conv2d_act(y, None, self.conv2.weight, self.conv2.bias, "none", self.precision, train)
             if self.fused == "on":
                 raise RuntimeError(f"FlowHead(fused='on'): {reason}")
 
@@ -215,14 +242,14 @@ class BasicUpdateBlock(nn.Module):
     """Network to compute single flow update delta (raft.py:276-296)"""
 
     def __init__(self, corr_planes, input_dim=128, hidden_dim=128, relu_inplace=True, *, gru_fused="off",
-                 gru_precision="fp32", fused="off", precision="fp32"):
+                 gru_precision="fp32", fused="off", precision="fp32", fused_backward=False):
         super().__init__()
 
-        self.enc = BasicMotionEncoder(corr_planes, fused=fused, precision=precision)
+        self.enc = BasicMotionEncoder(corr_planes, fused=fused, precision=precision, fused_backward=fused_backward)
         self.gru = SepConvGru(hidden_dim=hidden_dim, input_dim=input_dim+self.enc.output_dim, fused=gru_fused,
                               precision=gru_precision)
         self.flow = FlowHead(input_dim=hidden_dim, hidden_dim=256, relu_inplace=relu_inplace, fused=fused,
-                             precision=precision)
+                             precision=precision, fused_backward=fused_backward)
 
     def forward(self, h, x, corr, flow):
         m = self.enc(flow, corr)            # motion features
